@@ -30,6 +30,11 @@ null; ``reference_bound_ms_per_round`` records its implied upper bound (3 knight
 
 Launch: ``python bench.py --gpus 1`` or, for N > 1,
 ``python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N``.
+
+A plain run sets up, warms up, times ``--steps`` rounds and prints the result line; everything in
+the line comes from those rounds. ``--dump-outputs DIR`` also writes the last timed round's replies
+(token ids per knight) as ``.npy``; ``--full`` is where measurements that need runs of their own
+belong (none today).
 """
 from __future__ import annotations
 
@@ -104,6 +109,14 @@ def parse():
                         "ends in a forced consensus JSON scoring 6, then 9 in this round, so the tables reach "
                         "consensus and stop there (0 = off; use warmup + steps to end inside the timed region)")
     p.add_argument("--out", default=None, help="also write the JSON line to this file")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed rounds, write what the last timed round returned to the orchestrator: "
+                        "every knight's reply token ids as DIR/reply_ids.<knight>.npy (float64, one value per "
+                        "token). Prompts, weights and sampling are seeded, so two builds can be compared id for id")
+    p.add_argument("--full", action="store_true",
+                   help="also run the benchmark's secondary measurements. There are none today (the record's "
+                        "'detail' comes from the timed rounds themselves), so the flag changes nothing; anything "
+                        "added later that needs a run of its own goes behind it")
     p.add_argument("--stage-timeout", type=float, default=240.0,
                    help="seconds any stage (a round, a capture) may take on any rank, and the process-group "
                         "collective timeout; past it rank 0 prints the failure line and every rank exits")
@@ -296,6 +309,20 @@ def _run(args, failsafe) -> int:
     load_s = time.perf_counter() - t_load
 
     failsafe.set_stage("setup")
+    last_replies = {"round": None, "ids": {}}     # --dump-outputs: the newest round's replies, per knight
+    knight_cls = RemoteKnight
+    if args.dump_outputs:
+        class knight_cls(RemoteKnight):
+            """Keeps what the pool returns to the orchestrator for the newest round."""
+
+            def execute_group(self, pairs, timeout_s):
+                res = super().execute_group(pairs, timeout_s)
+                for (k, req), r in zip(pairs, res):
+                    if last_replies["round"] != req.round:
+                        last_replies["round"], last_replies["ids"] = req.round, {}
+                    if not isinstance(r, BaseException) and r.ids is not None:
+                        last_replies["ids"][k.knight_name] = list(r.ids)
+                return res
     rounds = args.warmup + args.steps
     workdir = tempfile.mkdtemp(prefix=f"rt-bench-r{cl.rank}-")
     orchs = []
@@ -306,7 +333,7 @@ def _run(args, failsafe) -> int:
                       "escalate_to_user_after": rounds + 1, "auto_execute": False, "ignore": [".git"],
                       "round_mode": args.round_mode, "prompt_layout": args.layout},
             "chronicle": ".roundtable/chronicle.md", "adapter_config": {}})
-        backends = {k["adapter"]: RemoteKnight(pool, k["name"], k["name"], k["adapter"]) for k in knights}
+        backends = {k["adapter"]: knight_cls(pool, k["name"], k["name"], k["adapter"]) for k in knights}
         # every rank runs every table (SPMD), but only the rank leading the table's first knight
         # writes its session files: per-rank host work stays one table's as N grows
         persist = placement[knights[0]["name"]][0] == cl.rank
@@ -474,6 +501,14 @@ def _run(args, failsafe) -> int:
     if args.c1_events:
         with open(f"{args.c1_events}.r{cl.rank}.json", "w") as f:
             json.dump({"rank": cl.rank, "events": pool.events, "ns": pool.event_ns}, f)
+    if cl.rank == 0 and args.dump_outputs:
+        import numpy as np
+        if last_replies["round"] != last:
+            raise SystemExit(f"--dump-outputs: the newest recorded round is {last_replies['round']}, not the "
+                             f"last timed round {last}")
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, ids in sorted(last_replies["ids"].items()):
+            np.save(os.path.join(args.dump_outputs, f"reply_ids.{name}.npy"), np.asarray(ids, dtype=np.float64))
     if cl.rank == 0:
         line = json.dumps(out)
         print(line, flush=True)

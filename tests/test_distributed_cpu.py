@@ -275,6 +275,28 @@ def _bench_single(extra=()):
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """bench.py --dump-outputs DIR writes the last timed round's replies (one float array of token
+    ids per knight); two runs with the same arguments write the same arrays, and recording them
+    (like --full, which adds nothing today) does not change the run."""
+    import numpy as np
+    recs, dumps = [], []
+    for d in ("a", "b"):
+        recs.append(_bench_single(("--dump-outputs", str(tmp_path / d), "--full")))
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == [f"reply_ids.{n}-0.npy" for n in ("Claude", "GPT", "Gemini")]
+        dumps.append([np.load(tmp_path / d / f) for f in files])
+    for a, b in zip(*dumps):
+        assert a.dtype == np.float64 and a.shape == (8,) and np.array_equal(a, b)
+        assert np.array_equal(a, a.astype(np.int64)) and a.min() >= 0
+    assert recs[0]["steps"] == 2 and recs[0]["ms_per_step"] > 0
+    assert recs[0]["detail"]["decode_tokens"] == 3 * 8 * 2
+    plain = _bench_single()
+    assert recs[0]["detail"]["transcript_sha"] == recs[1]["detail"]["transcript_sha"] == plain["detail"]["transcript_sha"]
+    assert {k: plain[k] for k in ("metric", "unit", "higher_is_better", "dtype", "steps")} == \
+           {k: recs[0][k] for k in ("metric", "unit", "higher_is_better", "dtype", "steps")}
+
+
 def test_bench_gpus_flag_self_launches_ranks():
     """`python bench.py --gpus 4` without a launcher starts 4 ranks itself (child torchrun) and
     reports them — never a silent 1-GPU run. Default strong scaling: one table
