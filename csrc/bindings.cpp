@@ -82,6 +82,16 @@ int launch_kv_block_copy(void* k, void* v, const int* src, const int* dst, int n
                          int64_t block_elems, hipStream_t stream);
 int launch_unshuffle_weight(void* W, const void* Ws, int N, int K, int rope_rows, int D, int swiglu,
                             hipStream_t stream);
+int launch_shuffle_weight_fp8(void* Wq, float* scale, float* amax, const void* W, const void* gamma, int N, int K,
+                              int rope_rows, int D, int swiglu, hipStream_t stream);
+int launch_unshuffle_weight_fp8(void* W, const void* Wq, const float* scale, int N, int K, int rope_rows, int D,
+                                int swiglu, hipStream_t stream);
+int launch_skinny_gemm_fp8(void* out, const void* x, const void* Wq, const float* scale, void* res, int M, int N,
+                           int K, int ldo, float eps, int pro, int epi, const void* rope, hipStream_t stream);
+int launch_skinny_gemm_rope_fp8(void* q_out, const void* x, const void* Wq, const float* scale, int M, int K, int pro,
+                                float eps, const int64_t* positions, const float* cos_sin, void* k_cache,
+                                void* v_cache, const int64_t* slots, int Hq, int Hkv, int D, int BS,
+                                const float* bias, hipStream_t stream);
 
 
 namespace {
@@ -672,6 +682,103 @@ void kv_block_copy(torch::Tensor k, torch::Tensor v, torch::Tensor src, torch::T
                                       (int)src.numel(), (int)k.size(0), (int)nb, k.size(2), cur_stream());
   TORCH_CHECK(rc == 0, "kv_block_copy: unsupported configuration (rc=", rc, ")");
 }
+
+// ---- FP8 weight-only decode GEMMs (csrc/gemm_skinny_fp8.hip) --------------------------------
+void check_fp8_weight(const torch::Tensor& Wq, const torch::Tensor& scale, int64_t rows, int64_t K, const char* who) {
+  check_type(Wq, torch::kUInt8, "Wq");
+  check_type(scale, torch::kFloat32, "wscale");
+  TORCH_CHECK(Wq.dim() == 2 && Wq.size(0) == rows && Wq.size(1) == K, who, ": Wq must be uint8 [N, K]");
+  TORCH_CHECK(scale.numel() == rows, who, ": wscale must have one entry per weight row");
+  TORCH_CHECK(K % 64 == 0 && rows % 16 == 0, who, ": fp8 weights need K % 64 == 0 and N % 16 == 0");
+}
+void shuffle_weight_fp8(torch::Tensor Wq, torch::Tensor scale, torch::Tensor W, c10::optional<torch::Tensor> gamma,
+                        int64_t rope_heads, int64_t head_dim, bool swiglu) {
+  check_bf16(W, "W");
+  TORCH_CHECK(W.dim() == 2, "shuffle_weight_fp8: W must be [N, K]");
+  check_fp8_weight(Wq, scale, W.size(0), W.size(1), "shuffle_weight_fp8");
+  const void* gp = nullptr;
+  if (gamma.has_value()) {
+    check_bf16(*gamma, "gamma");
+    TORCH_CHECK(gamma->numel() == W.size(1), "gamma must have K elements");
+    gp = gamma->data_ptr();
+  }
+  auto amax = torch::empty_like(scale);   // scratch between the two passes
+  const int rc = launch_shuffle_weight_fp8(Wq.data_ptr(), scale.data_ptr<float>(), amax.data_ptr<float>(),
+                                           W.data_ptr(), gp, (int)W.size(0), (int)W.size(1),
+                                           (int)(rope_heads * head_dim), (int)head_dim, swiglu ? 1 : 0, cur_stream());
+  TORCH_CHECK(rc == 0, "shuffle_weight_fp8: unsupported configuration (rc=", rc, ")");
+}
+void unshuffle_weight_fp8(torch::Tensor W, torch::Tensor Wq, torch::Tensor scale, int64_t rope_heads,
+                          int64_t head_dim, bool swiglu) {
+  check_bf16(W, "W");
+  TORCH_CHECK(W.dim() == 2, "unshuffle_weight_fp8: W must be [N, K]");
+  check_fp8_weight(Wq, scale, W.size(0), W.size(1), "unshuffle_weight_fp8");
+  const int rc = launch_unshuffle_weight_fp8(W.data_ptr(), Wq.data_ptr(), scale.data_ptr<float>(), (int)W.size(0),
+                                             (int)W.size(1), (int)(rope_heads * head_dim), (int)head_dim,
+                                             swiglu ? 1 : 0, cur_stream());
+  TORCH_CHECK(rc == 0, "unshuffle_weight_fp8: unsupported configuration (rc=", rc, ")");
+}
+// as skinny_gemm with uint8 fragment-order codes + per-row scales; M <= 16, pro PLAIN / NORM
+void skinny_gemm_fp8(torch::Tensor out, torch::Tensor x, torch::Tensor Wq, torch::Tensor scale, int64_t pro,
+                     int64_t epi, c10::optional<torch::Tensor> res, double eps) {
+  check_bf16(x, "x");
+  TORCH_CHECK(x.dim() == 2, "skinny_gemm_fp8: x [M, K]");
+  const int64_t M = x.size(0), K = x.size(1);
+  check_fp8_weight(Wq, scale, Wq.dim() == 2 ? Wq.size(0) : 0, K, "skinny_gemm_fp8");
+  TORCH_CHECK(M >= 1 && M <= 16, "skinny_gemm_fp8: 1 <= M <= 16");
+  TORCH_CHECK(pro == 0 || pro == 1, "skinny_gemm_fp8: prologue PLAIN or NORM");
+  TORCH_CHECK(epi >= 0 && epi <= 2, "skinny_gemm_fp8: epilogue STORE, RESID or SWIGLU");
+  int64_t N = Wq.size(0);
+  if (epi == 2) {
+    TORCH_CHECK(N % 32 == 0, "swiglu W must stack [gate; up]");
+    N /= 2;
+  }
+  void* rp = nullptr;
+  int64_t ldo = N;
+  if (epi == 1) {
+    TORCH_CHECK(res.has_value(), "resid epilogue needs res");
+    check_bf16(*res, "res");
+    TORCH_CHECK(res->dim() == 2 && res->size(0) == M && res->size(1) == N, "resid epilogue shapes");
+    rp = res->data_ptr();
+  } else {
+    check_bf16(out, "out");
+    TORCH_CHECK(out.dim() == 2 && out.size(0) == M && out.size(1) == N, "out must be [M, N]");
+    ldo = out.stride(0);
+  }
+  const int rc = launch_skinny_gemm_fp8(epi == 1 ? nullptr : out.data_ptr(), x.data_ptr(), Wq.data_ptr(),
+                                        scale.data_ptr<float>(), rp, (int)M, (int)N, (int)K, (int)ldo, (float)eps,
+                                        (int)pro, (int)epi, nullptr, cur_stream());
+  TORCH_CHECK(rc == 0, "skinny_gemm_fp8: unsupported configuration (rc=", rc, ")");
+}
+void skinny_gemm_rope_fp8(torch::Tensor q_out, torch::Tensor x, torch::Tensor Wq, torch::Tensor scale, int64_t pro,
+                          torch::Tensor positions, torch::Tensor cos_sin, torch::Tensor k_cache,
+                          torch::Tensor v_cache, torch::Tensor slots, int64_t Hq, int64_t Hkv, int64_t D, double eps,
+                          c10::optional<torch::Tensor> bias) {
+  check_bf16(q_out, "q_out");
+  check_bf16(x, "x");
+  TORCH_CHECK(x.dim() == 2, "skinny_gemm_rope_fp8: x [M, K]");
+  const int64_t M = x.size(0), K = x.size(1);
+  check_fp8_weight(Wq, scale, (Hq + 2 * Hkv) * D, K, "skinny_gemm_rope_fp8");
+  TORCH_CHECK(M >= 1 && M <= 16 && D % 16 == 0, "skinny_gemm_rope_fp8: 1 <= M <= 16, D % 16 == 0");
+  TORCH_CHECK(pro == 0 || pro == 1, "skinny_gemm_rope_fp8: prologue PLAIN or NORM");
+  TORCH_CHECK(q_out.numel() == M * Hq * D, "q_out must be [M, Hq, D]");
+  check_type(positions, torch::kInt64, "positions");
+  check_type(slots, torch::kInt64, "slots");
+  check_type(cos_sin, torch::kFloat32, "cos_sin");
+  TORCH_CHECK(positions.numel() >= M && slots.numel() >= M, "positions/slots must cover M rows");
+  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == D, "cos_sin must be [max_pos, D]");
+  check_caches(k_cache, v_cache, Hkv, D);
+  if (bias.has_value())
+    TORCH_CHECK(bias->scalar_type() == torch::kFloat32 && bias->is_contiguous() && bias->numel() == Wq.size(0) &&
+                    bias->device() == x.device(), "skinny_gemm_rope_fp8: bias must be contiguous fp32 [N] on x's device");
+  const int rc = launch_skinny_gemm_rope_fp8(q_out.data_ptr(), x.data_ptr(), Wq.data_ptr(), scale.data_ptr<float>(),
+                                             (int)M, (int)K, (int)pro, (float)eps, positions.data_ptr<int64_t>(),
+                                             cos_sin.data_ptr<float>(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                             slots.data_ptr<int64_t>(), (int)Hq, (int)Hkv, (int)D,
+                                             (int)k_cache.size(2), bias.has_value() ? bias->data_ptr<float>() : nullptr,
+                                             cur_stream());
+  TORCH_CHECK(rc == 0, "skinny_gemm_rope_fp8: unsupported configuration (rc=", rc, ")");
+}
 }  // namespace
 
 PYBIND11_MODULE(_C, m) {
@@ -688,6 +795,19 @@ PYBIND11_MODULE(_C, m) {
   m.def("kv_block_copy", &kv_block_copy, py::arg("k"), py::arg("v"), py::arg("src"), py::arg("dst"));
   m.def("unshuffle_weight", &unshuffle_weight, py::arg("W"), py::arg("Ws"), py::arg("rope_heads") = 0,
         py::arg("head_dim") = 0, py::arg("swiglu") = false);
+  m.def("shuffle_weight_fp8", &shuffle_weight_fp8, "quantise (e4m3fn, per-row scale) + fragment shuffle",
+        py::arg("Wq"), py::arg("scale"), py::arg("W"), py::arg("gamma") = py::none(), py::arg("rope_heads") = 0,
+        py::arg("head_dim") = 0, py::arg("swiglu") = false);
+  m.def("unshuffle_weight_fp8", &unshuffle_weight_fp8, "fragment-order codes + scales -> row-major bf16",
+        py::arg("W"), py::arg("Wq"), py::arg("scale"), py::arg("rope_heads") = 0, py::arg("head_dim") = 0,
+        py::arg("swiglu") = false);
+  m.def("skinny_gemm_fp8", &skinny_gemm_fp8, "decode GEMM (M<=16) on fp8 weights, fused norm / resid / swiglu",
+        py::arg("out"), py::arg("x"), py::arg("Wq"), py::arg("scale"), py::arg("pro"), py::arg("epi"),
+        py::arg("res") = py::none(), py::arg("eps") = 1e-5);
+  m.def("skinny_gemm_rope_fp8", &skinny_gemm_rope_fp8, "fp8-weight qkv decode GEMM with fused RoPE + K/V cache write",
+        py::arg("q_out"), py::arg("x"), py::arg("Wq"), py::arg("scale"), py::arg("pro"), py::arg("positions"),
+        py::arg("cos_sin"), py::arg("k_cache"), py::arg("v_cache"), py::arg("slots"), py::arg("Hq"), py::arg("Hkv"),
+        py::arg("D"), py::arg("eps") = 1e-5, py::arg("bias") = py::none());
   m.def("decode_prep", &decode_prep);
   m.def("oneshot_create", &py_oneshot_create, py::arg("world"), py::arg("rank"), py::arg("cap_elems"));
   m.def("oneshot_open", &py_oneshot_open, py::arg("id"), py::arg("all_handles"), py::arg("world"));

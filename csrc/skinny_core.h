@@ -24,6 +24,18 @@
 //             the SAME tile, sum in rank order; csrc/oneshot_ar.hip).
 // SC1 = true (persistent kernel): activations produced inside the same launch are read with
 // sc1 loads and every output is stored sc1 (write-through), MI355X_MICROARCH "Valid forms".
+//
+// FP8 weights (WT = WT_FP8, built by `shuffle_weight_fp8`, launched from gemm_skinny_fp8.hip):
+// OCP e4m3fn codes with one fp32 scale per weight row (W8A16: activations stay bf16). One record
+// is still 64 lanes x 16 B = 1 KiB, but 64 deep in k — a lane holds 16 CONSECUTIVE k of its row:
+//     Wq[N/16][K/64][64 lanes][16]  with  Wq[t][s][l][j] = code(W[16t + (l&15)][64s + 16(l>>4) + j])
+// (SwiGLU: [I/16][K/64][2][64][16], gate | up as for bf16). A "k-step" of the pipeline is then one
+// record = two MFMAs: bytes 8q..8q+7 (q = 0, 1) become the bf16 B fragment (exact: e4m3 fits in
+// bf16) against the A fragment x[m][64s + 16(l>>4) + 8q ..+8); the sum over k does not care that
+// the two MFMAs interleave k in 8s. The record order follows the bf16 rule of the same shape
+// (weight_order), with the chunks covering the same k range (half the records). scale[n] is
+// indexed by the epilogue's own column (ROPE: pair-interleaved rows; SwiGLU: gate rows [0, I),
+// up rows [I, 2I)) and multiplies the finished fp32 column sum after the 1/rms factor.
 #pragma once
 #include "common.h"
 
@@ -34,6 +46,12 @@ using rt::short8;
 
 enum : int { PRO_PLAIN = 0, PRO_NORM = 1, PRO_NORM_ADD = 2 };
 enum : int { EPI_STORE = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_ROPE = 3, EPI_AR = 4 };
+enum : int { WT_BF16 = 0, WT_FP8 = 1 };   // weight element type (header: FP8 weights)
+// MFMAs (32-deep A fragments) per weight record, k elements per record
+template <int WT>
+constexpr int kfrag() { return WT == WT_FP8 ? 2 : 1; }
+template <int WT>
+constexpr int kdeep() { return 32 * kfrag<WT>(); }
 
 struct RopeEpi {
   const int64_t* positions;  // [M]
@@ -73,6 +91,7 @@ struct GemmArgs {
   // 0 / c > 0 pinned (layout experiments, tools/exp_balance.hip)
   int kmajor = -1;
   ArEpi ar{};           // EPI_AR only
+  const float* wscale = nullptr;   // WT_FP8: per-row weight scales in the epilogue's column order
 };
 
 template <int NACC, int NW>   // NACC = accumulators per lane (2 for SwiGLU gate + up)
@@ -142,11 +161,11 @@ RT_DEVICE short8 ld_x8(const XSrc& x, int elem) {
 }
 
 // U = k-steps per wave per pipeline stage (x2 stages in flight)
-template <int PRO, int EPI, int U>
+template <int PRO, int EPI, int U, int WT = WT_BF16>
 struct Stage {
   short8 w[U];
   short8 w2[(EPI == EPI_SWIGLU) ? U : 1];
-  short8 a[U];
+  short8 a[U * kfrag<WT>()];
   short8 b[(PRO == PRO_NORM_ADD) ? U : 1];
 };
 
@@ -178,6 +197,23 @@ __host__ __device__ inline size_t rec_index(int t, int s, int T, int ks, int ord
   return ((size_t)(s >> lc) * T * C + (size_t)t * C + (s & (C - 1))) * recs;
 }
 
+// FP8: the record order of the bf16 weight of the same shape (K / 32 bf16 k-steps), the chunks
+// covering the same k range, i.e. half as many 64-deep records (k-major stays one record)
+__host__ __device__ inline int weight_order_fp8(int tiles, int K, bool swiglu, bool rope) {
+  return weight_order(tiles, K / 32, swiglu, rope);
+}
+// log2(records per chunk) of `order` > 0 for weight type WT
+template <int WT>
+__host__ __device__ inline int chunk_log2(int order) {
+  return WT == WT_FP8 ? (order >= 2 ? order - 2 : 0) : order - 1;
+}
+// rec_index for 64-deep fp8 records (s, ks in records)
+__host__ __device__ inline size_t rec_index_fp8(int t, int s, int T, int ks, int order, int recs) {
+  if (order <= 0) return ((size_t)t * ks + s) * recs;
+  const int lc = chunk_log2<WT_FP8>(order), C = 1 << lc;
+  return ((size_t)(s >> lc) * T * C + (size_t)t * C + (s & (C - 1))) * recs;
+}
+
 struct WStride {
   int lc;          // log2(k-steps per chunk) (30: tile-major, one chunk)
   size_t cstride;  // records between consecutive chunks of one tile
@@ -186,8 +222,8 @@ struct WStride {
   }
 };
 
-template <int PRO, int EPI, int NW, int U>
-RT_DEVICE void issue_w(Stage<PRO, EPI, U>& st, const short8* __restrict__ wt, const short8* __restrict__ wt2, int s0,
+template <int PRO, int EPI, int NW, int U, int WT = WT_BF16>
+RT_DEVICE void issue_w(Stage<PRO, EPI, U, WT>& st, const short8* __restrict__ wt, const short8* __restrict__ wt2, int s0,
                        int nsteps, int lane, WStride ws) {
   // SwiGLU weights are stored k-step-paired ([tile][step][gate|up][64 lanes][8]): one wave streams
   // 2 KiB contiguous per step instead of two 1-KiB streams 117 MB apart (`wt2` unused)
@@ -203,40 +239,80 @@ RT_DEVICE void issue_w(Stage<PRO, EPI, U>& st, const short8* __restrict__ wt, co
 }
 
 // first record of `tile` and the distance between its k-steps, for either weight order
-template <int EPI>
+template <int EPI, int WT = WT_BF16>
 RT_DEVICE const short8* tile_base(const GemmArgs& p, int tile, WStride& ws) {
-  const size_t T = (size_t)p.N / 16, ks = (size_t)p.K / 32;
-  const int order = p.kmajor >= 0 ? p.kmajor : weight_order((int)T, (int)ks, EPI == EPI_SWIGLU, EPI == EPI_ROPE);
+  const size_t T = (size_t)p.N / 16, ks = (size_t)p.K / kdeep<WT>();
+  const int order = p.kmajor >= 0 ? p.kmajor
+                                  : weight_order((int)T, p.K / 32, EPI == EPI_SWIGLU, EPI == EPI_ROPE);
   if (order <= 0) {
     ws.lc = 30;
     ws.cstride = 0;
     return p.Ws + (size_t)tile * ks * krec<EPI>();
   }
-  ws.lc = order - 1;
+  ws.lc = chunk_log2<WT>(order);
   const size_t chunk = (size_t)1 << ws.lc;
   ws.cstride = T * chunk * krec<EPI>();
   return p.Ws + (size_t)tile * chunk * krec<EPI>();
 }
 
-template <int PRO, int EPI, int NW, int U, bool SC1>
-RT_DEVICE void issue_a(Stage<PRO, EPI, U>& st, const XSrc& xr, const XSrc& xr2, bool row_ok, int s0, int nsteps) {
+template <int PRO, int EPI, int NW, int U, bool SC1, int WT = WT_BF16>
+RT_DEVICE void issue_a(Stage<PRO, EPI, U, WT>& st, const XSrc& xr, const XSrc& xr2, bool row_ok, int s0, int nsteps) {
   // unconditional as issue_w: lanes of rows >= M read row 0 (their MFMA rows and row sums are
   // never stored), steps past the end re-read the last one
   (void)row_ok;
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const int s = min(s0 + NW * u, nsteps - 1);
-    st.a[u] = ld_x8<SC1>(xr, s * 32);
+    if constexpr (WT == WT_FP8) {
+      // the lane's 16 consecutive k of the record: two A fragments, 32 B contiguous
+      st.a[2 * u] = ld_x8<SC1>(xr, s * 64);
+      st.a[2 * u + 1] = ld_x8<SC1>(xr, s * 64 + 8);
+    } else {
+      st.a[u] = ld_x8<SC1>(xr, s * 32);
+    }
     if constexpr (PRO == PRO_NORM_ADD) st.b[u] = ld_x8<SC1>(xr2, s * 32);
   }
 }
 
-template <int PRO, int EPI, int NW, int U, bool SC1>
-RT_DEVICE void consume(const Stage<PRO, EPI, U>& st, float4_& acc, float4_& acc2, float& ssq, int s0, int nsteps,
+// bytes 8q .. 8q+7 of an fp8 record lane (e4m3fn codes) as a bf16 MFMA fragment: one
+// v_cvt_scalef32_pk_bf16_fp8 per pair, exact
+typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4_ __attribute__((ext_vector_type(4)));
+RT_DEVICE bf16x8 fp8_frag(const short8& w, int q) {
+  const u32x4_ c = __builtin_bit_cast(u32x4_, w);
+  const unsigned lo = q ? c[2] : c[0], hi = q ? c[3] : c[1];
+  const bf16x2_ p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false);
+  const bf16x2_ p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true);
+  const bf16x2_ p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false);
+  const bf16x2_ p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true);
+  return bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+}
+
+template <int PRO, int EPI, int NW, int U, bool SC1, int WT = WT_BF16>
+RT_DEVICE void consume(const Stage<PRO, EPI, U, WT>& st, float4_& acc, float4_& acc2, float& ssq, int s0, int nsteps,
                        uint16_t* __restrict__ xo_r, const XSrc& xo_s) {
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     if (s0 + NW * u < nsteps) {
+      if constexpr (WT == WT_FP8) {
+        static_assert(PRO != PRO_NORM_ADD, "fp8 weights: plain / norm prologues");
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const short8 aq = st.a[2 * u + q];
+          const bf16x8 a = __builtin_bit_cast(bf16x8, aq);
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, fp8_frag(st.w[u], q), acc, 0, 0, 0);
+          if constexpr (EPI == EPI_SWIGLU)
+            acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, fp8_frag(st.w2[u], q), acc2, 0, 0, 0);
+          if constexpr (PRO != PRO_PLAIN) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+              const float f = rt::bf2f((uint16_t)aq[j]);
+              ssq = fmaf(f, f, ssq);
+            }
+          }
+        }
+        continue;
+      }
       short8 av = st.a[u];
       if constexpr (PRO == PRO_NORM_ADD) {
 #pragma unroll
@@ -497,41 +573,43 @@ RT_DEVICE void ar_exchange(const GemmArgs& p, int tile, float v, int m, int n, b
 // AC (persistent kernels): coherence of the ACTIVATION loads apart from the stores — -1 = as SC1,
 // 0 = plain (the activation came from an earlier launch), 1 = sc1 (produced in this launch). With
 // ALDS, AC = 1 stages the rows with sc1 loads once, then reads LDS.
-template <int PRO, int EPI, int NW, int U, bool SC1, bool ALDS = false, int AC = -1>
-RT_DEVICE void gemm_tile(const GemmArgs& p, int tile, GemmSmem<nacc<EPI>(), NW>& sm, Stage<PRO, EPI, U>& st0,
+template <int PRO, int EPI, int NW, int U, bool SC1, bool ALDS = false, int AC = -1, int WT = WT_BF16>
+RT_DEVICE void gemm_tile(const GemmArgs& p, int tile, GemmSmem<nacc<EPI>(), NW>& sm, Stage<PRO, EPI, U, WT>& st0,
                          bool prefetched,
                          bool publish_xo, const SplitX* sx = nullptr, const ALds* al = nullptr) {
   constexpr bool SC1A = AC < 0 ? SC1 : AC != 0;
   static_assert(!(ALDS && SC1 && AC < 0), "an LDS-staged A operand in a persistent launch needs an explicit AC");
+  static_assert(WT == WT_BF16 || (!ALDS && !SC1 && PRO != PRO_NORM_ADD && EPI != EPI_AR),
+                "fp8 weights: one launch per GEMM, plain / norm prologues, no LDS-staged A, no all-reduce");
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 15, g = lane >> 4;
   const int M = p.M, N = p.N, K = p.K;
-  const int ksteps = K / 32;
+  const int ksteps = K / kdeep<WT>();
   // k-step range of this workgroup: all of K, or one part of a split tile. `nsteps` below is
   // the range END (loads clamp to it), `s_lo` its start.
   const int s_lo = sx != nullptr ? (int)((long)ksteps * sx->idx / sx->n) : 0;
   const int nsteps = sx != nullptr ? (int)((long)ksteps * (sx->idx + 1) / sx->n) : ksteps;
   const bool row_ok = r < M;
-  const size_t lane_elem = (size_t)(row_ok ? r : 0) * K + 8 * g;
+  const size_t lane_elem = (size_t)(row_ok ? r : 0) * K + 8 * kfrag<WT>() * g;
   const XSrc xr = make_xsrc<SC1A>(p.x, lane_elem);
   const XSrc xr2 = make_xsrc<SC1A>(PRO == PRO_NORM_ADD ? p.x2 : p.x, lane_elem);
   uint16_t* xo_r =
       (PRO == PRO_NORM_ADD && publish_xo && row_ok && p.xo != nullptr) ? p.xo + (size_t)r * K + 8 * g : nullptr;
   const XSrc xo_s = make_xsrc<SC1A>(PRO == PRO_NORM_ADD && p.xo != nullptr ? p.xo : p.x, lane_elem);
   WStride sstride;
-  const short8* wt = tile_base<EPI>(p, tile, sstride);
+  const short8* wt = tile_base<EPI, WT>(p, tile, sstride);
   const short8* wt2 = nullptr;
 
   float4_ acc = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f};
   float ssq = 0.f;
-  Stage<PRO, EPI, U> st1;
+  Stage<PRO, EPI, U, WT> st1;
   // stages of this wave: s = wid + NW*U*j < nsteps. Both halves of a pair sit in ONE basic
   // block (a break between them lets MachineSink move each stage's loads down next to their
   // consumer); every issue is unconditional, so the waits are counted, not vmcnt(0).
   constexpr int SPAN = NW * U;
   const int w0 = s_lo + wid;   // this wave's first k-step
   const int nst = w0 < nsteps ? (nsteps - w0 + SPAN - 1) / SPAN : 0;
-  if (!prefetched) issue_w<PRO, EPI, NW, U>(st0, wt, wt2, w0, nsteps, lane, sstride);
+  if (!prefetched) issue_w<PRO, EPI, NW, U, WT>(st0, wt, wt2, w0, nsteps, lane, sstride);
   const uint16_t* arow = nullptr;
   if constexpr (ALDS) {
     // stage-0 weights are in flight; stage A once (its loads overlap theirs), then the k-loop
@@ -540,7 +618,7 @@ RT_DEVICE void gemm_tile(const GemmArgs& p, int tile, GemmSmem<nacc<EPI>(), NW>&
     __syncthreads();
     arow = al->a + (size_t)(row_ok ? r : 0) * al->astride + 8 * g - 32 * s_lo;
   } else {
-    issue_a<PRO, EPI, NW, U, SC1A>(st0, xr, xr2, row_ok, w0, nsteps);
+    issue_a<PRO, EPI, NW, U, SC1A, WT>(st0, xr, xr2, row_ok, w0, nsteps);
   }
   // Epilogue operands that do not depend on the GEMM are loaded NOW, so their round trips hide
   // under the k-loop instead of following the last MFMA: the residual element (RESID) and the
@@ -549,6 +627,14 @@ RT_DEVICE void gemm_tile(const GemmArgs& p, int tile, GemmSmem<nacc<EPI>(), NW>&
   const int em = min((int)(threadIdx.x >> 4), M - 1), en = threadIdx.x & 15;
   float e_res = 0.f, e_c = 0.f, e_s = 0.f, e_b = 0.f, e_bp = 0.f;
   int64_t e_slot = 0;
+  // fp8: this column's weight scale and its second one (SwiGLU: the up row's; ROPE: the
+  // rotate-half partner's, column ^ 1)
+  float e_w = 1.f, e_w2 = 1.f;
+  if constexpr (WT == WT_FP8) {
+    e_w = p.wscale[tile * 16 + en];
+    if constexpr (EPI == EPI_SWIGLU) e_w2 = p.wscale[N + tile * 16 + en];
+    if constexpr (EPI == EPI_ROPE) e_w2 = p.wscale[(tile * 16 + en) ^ 1];
+  }
   if constexpr (EPI == EPI_RESID) e_res = ld16<SC1>(p.res + (size_t)em * N + tile * 16 + en);
   if constexpr (EPI == EPI_ROPE) {
     const RopeEpi& re = p.re;
@@ -566,23 +652,23 @@ RT_DEVICE void gemm_tile(const GemmArgs& p, int tile, GemmSmem<nacc<EPI>(), NW>&
   if constexpr (ALDS) {
     for (; j + 1 < nst; j += 2) {
       const int s = w0 + SPAN * j;
-      issue_w<PRO, EPI, NW, U>(st1, wt, wt2, s + SPAN, nsteps, lane, sstride);
+      issue_w<PRO, EPI, NW, U, WT>(st1, wt, wt2, s + SPAN, nsteps, lane, sstride);
       consume_lds<PRO, EPI, NW, U>(st0, acc, acc2, s, nsteps, arow);
-      issue_w<PRO, EPI, NW, U>(st0, wt, wt2, s + 2 * SPAN, nsteps, lane, sstride);
+      issue_w<PRO, EPI, NW, U, WT>(st0, wt, wt2, s + 2 * SPAN, nsteps, lane, sstride);
       consume_lds<PRO, EPI, NW, U>(st1, acc, acc2, s + SPAN, nsteps, arow);
     }
     if (j < nst) consume_lds<PRO, EPI, NW, U>(st0, acc, acc2, w0 + SPAN * j, nsteps, arow);
   } else {
     for (; j + 1 < nst; j += 2) {
       const int s = w0 + SPAN * j;
-      issue_w<PRO, EPI, NW, U>(st1, wt, wt2, s + SPAN, nsteps, lane, sstride);
-      issue_a<PRO, EPI, NW, U, SC1A>(st1, xr, xr2, row_ok, s + SPAN, nsteps);
-      consume<PRO, EPI, NW, U, SC1A>(st0, acc, acc2, ssq, s, nsteps, xo_r, xo_s);
-      issue_w<PRO, EPI, NW, U>(st0, wt, wt2, s + 2 * SPAN, nsteps, lane, sstride);
-      issue_a<PRO, EPI, NW, U, SC1A>(st0, xr, xr2, row_ok, s + 2 * SPAN, nsteps);
-      consume<PRO, EPI, NW, U, SC1A>(st1, acc, acc2, ssq, s + SPAN, nsteps, xo_r, xo_s);
+      issue_w<PRO, EPI, NW, U, WT>(st1, wt, wt2, s + SPAN, nsteps, lane, sstride);
+      issue_a<PRO, EPI, NW, U, SC1A, WT>(st1, xr, xr2, row_ok, s + SPAN, nsteps);
+      consume<PRO, EPI, NW, U, SC1A, WT>(st0, acc, acc2, ssq, s, nsteps, xo_r, xo_s);
+      issue_w<PRO, EPI, NW, U, WT>(st0, wt, wt2, s + 2 * SPAN, nsteps, lane, sstride);
+      issue_a<PRO, EPI, NW, U, SC1A, WT>(st0, xr, xr2, row_ok, s + 2 * SPAN, nsteps);
+      consume<PRO, EPI, NW, U, SC1A, WT>(st1, acc, acc2, ssq, s + SPAN, nsteps, xo_r, xo_s);
     }
-    if (j < nst) consume<PRO, EPI, NW, U, SC1A>(st0, acc, acc2, ssq, w0 + SPAN * j, nsteps, xo_r, xo_s);
+    if (j < nst) consume<PRO, EPI, NW, U, SC1A, WT>(st0, acc, acc2, ssq, w0 + SPAN * j, nsteps, xo_r, xo_s);
   }
 
   // C layout: acc[i] = C[m = 4g + i][n = r]
@@ -652,9 +738,11 @@ RT_DEVICE void gemm_tile(const GemmArgs& p, int tile, GemmSmem<nacc<EPI>(), NW>&
     float inv = 1.f;
     if constexpr (PRO != PRO_PLAIN) inv = rsqrtf(ss / (float)K + p.eps);
     v *= inv;
+    if constexpr (WT == WT_FP8) v *= e_w;
     const int col = tile * 16 + n;
     if constexpr (EPI == EPI_SWIGLU) {
       up *= inv;
+      if constexpr (WT == WT_FP8) up *= e_w2;
       st16<SC1>(p.out + (size_t)m * p.ldo + col, silu(v) * up);
     } else if constexpr (EPI == EPI_RESID) {
       uint16_t* rp = p.res + (size_t)m * N + col;
@@ -668,7 +756,7 @@ RT_DEVICE void gemm_tile(const GemmArgs& p, int tile, GemmSmem<nacc<EPI>(), NW>&
       const int off = (int)(slot - blk * re.BS);
       v += e_b;
       if (h < re.Hq + re.Hkv) {
-        const float partner = fmaf(vpartner, inv, e_bp);
+        const float partner = WT == WT_FP8 ? fmaf(vpartner * inv, e_w2, e_bp) : fmaf(vpartner, inv, e_bp);
         const int i = pp >> 1, hi = pp & 1;
         const float c = e_c, sn = e_s;
         // pair (x1 = d i, x2 = d i+D/2): y1 = x1 c - x2 s ; y2 = x2 c + x1 s

@@ -108,8 +108,21 @@ def validate_config(cfg: Dict[str, Any]) -> None:
         raise ConfigError("config.json missing 'adapter_config' section.")
 
 
+WEIGHT_QUANTS = ("none", "fp8")
+
+
+def resolve_weight_quant(value: Optional[str]) -> str:
+    """A stated ``weight_quant`` ("none" | "fp8"), or — when a config says nothing (None / "") —
+    the ROUNDTABLE_WEIGHT_QUANT default, else "none"."""
+    q = str(value if value else os.environ.get("ROUNDTABLE_WEIGHT_QUANT") or "none").lower()
+    if q not in WEIGHT_QUANTS:
+        raise ConfigError(f"unknown weight_quant {q!r}", hint=f"One of: {', '.join(WEIGHT_QUANTS)}.")
+    return q
+
+
 def engine_settings(config: RoundtableConfig, adapter_id: str) -> Dict[str, Any]:
-    """Effective engine settings for one adapter id: defaults <- config.engine <- adapter engine."""
+    """Effective engine settings for one adapter id: defaults <- config.engine <- adapter engine.
+    ``weight_quant`` (engine-wide or per knight) comes back resolved: "none" | "fp8"."""
     out = dict(ENGINE_DEFAULTS)
     top = config.raw.get("engine") if isinstance(config.raw, dict) else None
     if isinstance(top, dict):
@@ -121,6 +134,7 @@ def engine_settings(config: RoundtableConfig, adapter_id: str) -> Dict[str, Any]
     if "model" not in out or not out.get("model"):
         out["model"] = resolve_model_name(ac.get("model") if isinstance(ac, dict) else None,
                                           out["default_model"])
+    out["weight_quant"] = resolve_weight_quant(out.get("weight_quant"))
     return out
 
 

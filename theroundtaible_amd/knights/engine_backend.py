@@ -11,6 +11,7 @@ from __future__ import annotations
 import threading
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
+from ..config import resolve_weight_quant
 from ..engine.engine import Engine, EngineConfig, Turn
 from ..engine.sampler import SamplingParams
 from .base import KnightBackend, TurnRequest, TurnResult
@@ -88,7 +89,9 @@ class EnginePool:
 
     def get(self, ecfg: EngineConfig, defer_kv: bool = False) -> Tuple[Engine, threading.Lock]:
         """``defer_kv``: load weights only; :meth:`finalize` sizes the KV pools afterwards."""
-        key = (ecfg.model, ecfg.weights, ecfg.dtype, ecfg.device, ecfg.block_size)
+        # (a bf16 knight and an fp8 knight of the same model never share an engine)
+        key = (ecfg.model, ecfg.weights, ecfg.dtype, ecfg.device, ecfg.block_size,
+               resolve_weight_quant(ecfg.weight_quant))
         if key not in self.engines:
             if defer_kv and ecfg.num_blocks is None and ecfg.kv_budget_bytes is None:
                 ecfg.defer_kv = True

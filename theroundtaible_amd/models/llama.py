@@ -85,6 +85,12 @@ class LlamaModel:
         cfg = self.cfg
         rows = 32 if self.tp.size == 1 and not self.force_tp_path else 16
         rows = min(rows, int(os.environ.get("ROUNDTABLE_FUSED_ROWS", rows)))   # A/B knob
+        if self.quant == "fp8":
+            # tp 1 only, <= 32 rows (two launches of 16); more rows take the unfused path on
+            # operands dequantised into scratch (correct, slow)
+            if self.tp.size != 1 or self.force_tp_path:
+                return False
+            rows = min(rows, ops.FP8_MAX_ROWS)
         return (ids.is_cuda and 1 <= ids.shape[0] <= rows and self.use_fused
                 and cfg.hidden % 32 == 0 and cfg.ffn % 32 == 0 and (cfg.n_heads * cfg.head_dim) % 32 == 0
                 and self.lm_rows % 16 == 0)
@@ -98,24 +104,59 @@ class LlamaModel:
     # (gamma-folded) operand in a per-shape scratch buffer with ops.unshuffle_weight
     shuffled_only = False
     _scratch: Optional[Dict[tuple, torch.Tensor]] = None
+    # weight quantisation of the decode linears: None | "fp8" (e4m3fn codes + per-row scales,
+    # csrc/gemm_skinny_fp8.hip). Always single-copy: the dequantised row-major operand of the
+    # prefill / unfused GEMMs is rebuilt in the same scratch as shuffled-only residency, so every
+    # path computes with the SAME weights bf16(code * scale)
+    quant: Optional[str] = None
+
+    def fp8_width_error(self) -> Optional[str]:
+        """Why this model's GEMM depths do not fit the fp8 k-record (None: they fit)."""
+        cfg = self.cfg
+        for what, k in (("hidden", cfg.hidden), ("ffn / tp", cfg.ffn // self.tp.size),
+                        ("heads x head_dim / tp", self.n_heads * self.head_dim)):
+            if k % ops.FP8_K_RECORD:
+                return f"{what} = {k} is not a multiple of the fp8 k-record ({ops.FP8_K_RECORD})"
+        if self.lm_rows % 16:
+            return f"lm_head rows = {self.lm_rows} is not a multiple of 16"
+        return None
 
     # (name, folded norm, shuffle kwargs) of the linears the fused decode path streams
     def _lin_specs(self):
         return (("wqkv", "attn_norm", {"rope_heads": self.n_heads + self.n_kv_heads, "head_dim": self.head_dim}),
                 ("wo", None, {}), ("w_gate_up", "ffn_norm", {"swiglu": True}), ("w_down", None, {}))
 
-    def decode_weights(self, drop_originals: bool = False):
+    def decode_weights(self, drop_originals: bool = False, quant: Optional[str] = None):
         """Fragment-shuffled, norm-folded copies of every linear for the fused decode path (built
         lazily once). Default: +1x weight memory, affordable on 288 GB HBM for 7-8B knights.
         ``drop_originals``: shuffle one linear at a time and free its row-major tensor (peak +1
-        tensor), so only ONE copy of the weights stays resident (see :attr:`shuffled_only`)."""
+        tensor), so only ONE copy of the weights stays resident (see :attr:`shuffled_only`).
+        ``quant="fp8"``: quantise each linear instead (``name`` -> uint8 codes, ``name_scale`` ->
+        fp32 row scales); always drops the originals. The embedding table stays bf16 (a tied
+        lm_head loses only its own reference)."""
         if self._dec is None:
+            if quant not in (None, "none", "fp8"):
+                raise ValueError(f"unknown weight quantisation {quant!r}")
+            fp8 = quant == "fp8"
+            if fp8:
+                err = self.fp8_width_error()
+                if err or self.tp.size != 1:
+                    raise ValueError(f"{self.cfg.name}: fp8 weights: {err or 'tensor parallel is not supported'}")
+                drop_originals = True
+                self.quant = "fp8"
+
+            def shuffle(W, gamma, d, name, **kw):
+                if fp8:
+                    d[name], d[name + "_scale"] = ops.shuffle_weight_fp8(W, gamma, **kw)
+                else:
+                    d[name] = ops.shuffle_weight(W, gamma, **kw)
+
             with torch.no_grad():
                 layers = []
                 for i, lw in enumerate(self.layers):
                     d = {}
                     for name, norm, kw in self._lin_specs():
-                        d[name] = ops.shuffle_weight(lw[name], lw[norm] if norm else None, **kw)
+                        shuffle(lw[name], lw[norm] if norm else None, d, name, **kw)
                         if drop_originals:
                             # drop BOTH references (the per-layer view and the flat dict) now, so the
                             # allocator reuses this tensor's memory for the next shuffle: the load peak
@@ -125,7 +166,9 @@ class LlamaModel:
                     if lw.get("bqkv") is not None:   # Qwen2: the bias the qkv epilogue adds before RoPE
                         d["bqkv"] = ops.rope_bias(lw["bqkv"], self.n_heads, self.n_kv_heads, self.head_dim)
                     layers.append(d)
-                lm = ops.shuffle_weight(self.w["lm_head"], self.w["final_norm"])
+                top = {}
+                shuffle(self.w["lm_head"], self.w["final_norm"], top, "lm_head")
+                lm = top["lm_head"]
                 if drop_originals:
                     self.w["lm_head"] = None
                     for k in [k for k in self.w if k.startswith("layers.") and k.split(".", 2)[2] in
@@ -139,8 +182,9 @@ class LlamaModel:
                 # the engine's stream; counters re-arm at the end of each call): split-K for shard
                 # shapes with fewer tiles than CUs (tensor parallel), and the balanced launch of
                 # gate_up, whose tile count (ffn/16) is rarely a multiple of the CU count
-                ws = ops.split_workspace(lm.device) if lm.is_cuda else None
-                self._dec = {"layers": layers, "lm_head": lm, "split_ws": ws}
+                # (the fp8 launches have no split forms: no workspace)
+                ws = ops.split_workspace(lm.device) if lm.is_cuda and not fp8 else None
+                self._dec = {"layers": layers, "split_ws": ws, **top}
         return self._dec
 
     def _row_major(self, l: Optional[int], name: str) -> torch.Tensor:
@@ -149,14 +193,17 @@ class LlamaModel:
         if not self.shuffled_only:
             return self.layers[l][name] if l is not None else self.w[name]
         if l is None:
-            Ws, kw = self._dec["lm_head"], {}
+            d, kw = self._dec, {}
         else:
-            Ws = self._dec["layers"][l][name]
+            d = self._dec["layers"][l]
             kw = next(k for n, _, k in self._lin_specs() if n == name)
+        Ws = d[name]
         key = tuple(Ws.shape)
         buf = self._scratch.get(key)
         if buf is None:
-            buf = self._scratch[key] = torch.empty_like(Ws)
+            buf = self._scratch[key] = torch.empty(Ws.shape, dtype=self.dtype, device=Ws.device)
+        if self.quant == "fp8":
+            return ops.unshuffle_weight_fp8(Ws, d[name + "_scale"], out=buf, **kw)
         return ops.unshuffle_weight(Ws, out=buf, **kw)
 
     def _norm_w(self, l: Optional[int], name: str) -> torch.Tensor:
@@ -186,17 +233,20 @@ class LlamaModel:
         B = ids.shape[0]
         sw, SK, ALL = dec["split_ws"], ops.SPLIT_K, ops.SPLIT_K | ops.SPLIT_BALANCE
         for l, lw in enumerate(dec["layers"]):
+            # (``*_scale``: fp8 weights' row scales, absent = bf16)
             q = ops.skinny_gemm_rope(res, lw["wqkv"], ops.PRO_NORM, positions, self.cos_sin, kv.k_layer(l),
                                      kv.v_layer(l), meta.slot_mapping, self.n_heads, self.n_kv_heads,
-                                     self.head_dim, eps, split_ws=sw, split_mode=SK, bias=lw.get("bqkv"))
+                                     self.head_dim, eps, split_ws=sw, split_mode=SK, bias=lw.get("bqkv"),
+                                     wscale=lw.get("wqkv_scale"))
             a = self.attention(q, kv.k_layer(l), kv.v_layer(l), meta)
             ops.skinny_gemm(a.reshape(B, -1), lw["wo"], ops.PRO_PLAIN, ops.EPI_RESID, res=res, split_ws=sw,
-                            split_mode=SK)
+                            split_mode=SK, wscale=lw.get("wo_scale"))
             g = ops.skinny_gemm(res, lw["w_gate_up"], ops.PRO_NORM, ops.EPI_SWIGLU, eps=eps, split_ws=sw,
-                                split_mode=ALL)
-            ops.skinny_gemm(g, lw["w_down"], ops.PRO_PLAIN, ops.EPI_RESID, res=res, split_ws=sw, split_mode=SK)
+                                split_mode=ALL, wscale=lw.get("w_gate_up_scale"))
+            ops.skinny_gemm(g, lw["w_down"], ops.PRO_PLAIN, ops.EPI_RESID, res=res, split_ws=sw, split_mode=SK,
+                            wscale=lw.get("w_down_scale"))
         logits = ops.skinny_gemm(res, dec["lm_head"], ops.PRO_NORM, ops.EPI_STORE, eps=eps, split_ws=sw,
-                                 split_mode=SK)
+                                 split_mode=SK, wscale=dec.get("lm_head_scale"))
         return logits[:, :cfg.vocab]
 
     def forward_decode_fused_tp(self, ids: torch.Tensor, positions: torch.Tensor, kv, meta: AttnMeta,

@@ -399,17 +399,90 @@ def split_workspace(device) -> torch.Tensor:
     return torch.zeros(SPLIT_WS_INTS, dtype=torch.int32, device=device)
 
 
+FP8_K_RECORD = 64        # k elements per fp8 weight record (csrc/skinny_core.h): K must be a multiple
+FP8_MAX_ROWS = 32        # fused rows on fp8 weights: two launches of <= 16
+
+
+def shuffle_weight_fp8(W: torch.Tensor, gamma: Optional[torch.Tensor] = None, rope_heads: int = 0,
+                       head_dim: int = 0, swiglu: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """FP8 (OCP e4m3fn) weight-only quantisation of a decode linear: ``(Wq uint8 [N, K], scale
+    fp32 [N])`` with one scale per weight row, taken after the RMSNorm ``gamma`` fold
+    (:func:`reference.quantize_fp8` is the contract). On the GPU the codes are in the MFMA fragment
+    order of csrc/gemm_skinny_fp8.hip; on CPU they stay row-major. Rows (and their scales) are in the
+    order the epilogues index them: ``rope_heads`` leading heads pair-interleaved as
+    :func:`shuffle_weight`; ``swiglu`` keeps [gate; up]."""
+    N, K = W.shape
+    if K % FP8_K_RECORD or N % 16:
+        raise ValueError(f"fp8 weights need K % {FP8_K_RECORD} == 0 and N % 16 == 0 (got [{N}, {K}])")
+    if _use_native(W):
+        Wq = torch.empty(N, K, dtype=torch.uint8, device=W.device)
+        scale = torch.empty(N, dtype=torch.float32, device=W.device)
+        native().shuffle_weight_fp8(Wq, scale, W.contiguous(), gamma, int(rope_heads), int(head_dim), bool(swiglu))
+        return Wq, scale
+    return ref.quantize_fp8(W, gamma, rope_heads, head_dim)
+
+
+def unshuffle_weight_fp8(Wq: torch.Tensor, scale: torch.Tensor, rope_heads: int = 0, head_dim: int = 0,
+                         swiglu: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Row-major ``bf16(code * scale)`` in natural row order from a :func:`shuffle_weight_fp8`
+    pair: the operand of the prefill / unfused GEMMs (the fp8 twin of :func:`unshuffle_weight`)."""
+    if out is None:
+        out = torch.empty(Wq.shape, dtype=torch.bfloat16, device=Wq.device)
+    if _use_native(Wq):
+        native().unshuffle_weight_fp8(out, Wq, scale, int(rope_heads), int(head_dim), bool(swiglu))
+        return out
+    Wd = ref.dequantize_fp8(Wq, scale)
+    if rope_heads:
+        inv = torch.empty(Wq.shape[0], dtype=torch.long)
+        inv[ref.rope_row_perm(Wq.shape[0], rope_heads, head_dim)] = torch.arange(Wq.shape[0])
+        Wd = Wd[inv]
+    out.copy_(Wd)
+    return out
+
+
+def _fp8_check(x, Ws, wscale, pro, x2, xout, split_ws, who):
+    """The fp8 launch has the one-tile forms only: refuse everything else loudly."""
+    if Ws.dtype != torch.uint8:
+        raise ValueError(f"{who}: wscale given but Ws is {Ws.dtype}, not the uint8 codes of shuffle_weight_fp8")
+    if pro not in (PRO_PLAIN, PRO_NORM) or x2 is not None or xout is not None:
+        raise ValueError(f"{who}: fp8 weights take the PLAIN / NORM prologues only (no x2 / xout)")
+    if split_ws is not None:
+        raise ValueError(f"{who}: fp8 weights have no split-K / CU-balanced launch (pass split_ws=None)")
+    if x.shape[0] > FP8_MAX_ROWS:
+        raise ValueError(f"{who}: at most {FP8_MAX_ROWS} rows on fp8 weights (got {x.shape[0]})")
+    if x.shape[1] % FP8_K_RECORD:
+        raise ValueError(f"{who}: fp8 weights need K % {FP8_K_RECORD} == 0 (got {x.shape[1]})")
+
+
 def skinny_gemm(x: torch.Tensor, Ws: torch.Tensor, pro: int = PRO_PLAIN, epi: int = EPI_STORE,
                 res: Optional[torch.Tensor] = None, eps: float = 1e-5, x2: Optional[torch.Tensor] = None,
                 xout: Optional[torch.Tensor] = None, split_ws: Optional[torch.Tensor] = None,
-                split_mode: int = SPLIT_K | SPLIT_BALANCE) -> Optional[torch.Tensor]:
+                split_mode: int = SPLIT_K | SPLIT_BALANCE,
+                wscale: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
     """Decode linear (M <= 16; up to 32 with the plain / norm prologues) on shuffled weights with fused RMSNorm prologue (gamma pre-folded)
     and residual / SwiGLU epilogue. Returns the output (None for RESID, which updates ``res``).
     ``PRO_NORM_ADD``: normalizes ``bf16(x + x2)`` and writes that sum to ``xout`` (TP decode).
     ``split_ws`` (:func:`split_workspace`) enables, per ``split_mode`` bit: ``SPLIT_K`` — fewer
     tiles than CUs (tensor-parallel shards): each tile's K range runs as S workgroups whose last
     arriver combines; ``SPLIT_BALANCE`` — tile count not a multiple of the CU count: the remainder
-    tiles run as two K-halves so every CU streams the same bytes."""
+    tiles run as two K-halves so every CU streams the same bytes.
+    ``wscale``: ``Ws`` is the uint8 codes of :func:`shuffle_weight_fp8` and ``wscale`` its scales
+    (PLAIN / NORM prologues, no split workspace; 17..32 rows run as two launches of <= 16, rows
+    being independent in every epilogue)."""
+    if wscale is not None:
+        _fp8_check(x, Ws, wscale, pro, x2, xout, split_ws, "skinny_gemm")
+        if not _use_native(x):
+            return ref.skinny_gemm(x, ref.dequantize_fp8(Ws, wscale), pro, epi, res, eps)
+        M = x.shape[0]
+        n = Ws.shape[0] // (2 if epi == EPI_SWIGLU else 1)
+        out = torch.empty(M, n, dtype=x.dtype, device=x.device) if epi != EPI_RESID else x
+        for a in range(0, M, 16):
+            b = min(M, a + 16)
+            native().skinny_gemm_fp8(out[a:b], x[a:b], Ws, wscale, pro, epi, res[a:b] if res is not None else None,
+                                     eps)
+        return None if epi == EPI_RESID else out
+    if Ws.dtype == torch.uint8:
+        raise ValueError("skinny_gemm: uint8 (fp8) weights need their wscale")
     if _use_native(x):
         n = Ws.shape[0] // (2 if epi == EPI_SWIGLU else 1)
         out = torch.empty(x.shape[0], n, dtype=x.dtype, device=x.device) if epi != EPI_RESID else x
@@ -422,13 +495,30 @@ def skinny_gemm_rope(x: torch.Tensor, Ws: torch.Tensor, pro: int, positions: tor
                      k_cache: torch.Tensor, v_cache: torch.Tensor, slots: torch.Tensor, n_heads: int,
                      n_kv_heads: int, head_dim: int, eps: float = 1e-5, x2: Optional[torch.Tensor] = None,
                      xout: Optional[torch.Tensor] = None, split_ws: Optional[torch.Tensor] = None,
-                     split_mode: int = SPLIT_K | SPLIT_BALANCE, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     split_mode: int = SPLIT_K | SPLIT_BALANCE, bias: Optional[torch.Tensor] = None,
+                     wscale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Decode qkv projection (+ optional RMSNorm prologue) with RoPE and the paged K/V cache
     write fused into the epilogue; returns q [M, n_heads, head_dim]. ``Ws`` must come from
     ``shuffle_weight(Wqkv, gamma, rope_heads=n_heads + n_kv_heads, head_dim=head_dim)``.
     ``split_ws`` / ``split_mode``: as in :func:`skinny_gemm` (no balanced launch with ``PRO_NORM_ADD``).
     ``bias`` (Qwen2 q/k/v bias, added after the norm scale and before RoPE) must come from
-    :func:`rope_bias` (fp32, the shuffled weight's column order)."""
+    :func:`rope_bias` (fp32, the shuffled weight's column order).
+    ``wscale``: fp8 weights, as in :func:`skinny_gemm` (``Ws`` from ``shuffle_weight_fp8`` with the
+    same ``rope_heads`` / ``head_dim``)."""
+    if wscale is not None:
+        _fp8_check(x, Ws, wscale, pro, x2, xout, split_ws, "skinny_gemm_rope")
+        if not _use_native(x):
+            return ref.skinny_gemm_rope(x, ref.dequantize_fp8(Ws, wscale), pro, positions, cos_sin, k_cache,
+                                        v_cache, slots, n_heads, n_kv_heads, head_dim, eps, None, None, bias)
+        M = x.shape[0]
+        q = torch.empty(M, n_heads, head_dim, dtype=x.dtype, device=x.device)
+        for a in range(0, M, 16):
+            b = min(M, a + 16)
+            native().skinny_gemm_rope_fp8(q[a:b], x[a:b], Ws, wscale, pro, positions[a:b], cos_sin, k_cache, v_cache,
+                                          slots[a:b], n_heads, n_kv_heads, head_dim, eps, bias)
+        return q
+    if Ws.dtype == torch.uint8:
+        raise ValueError("skinny_gemm_rope: uint8 (fp8) weights need their wscale")
     if _use_native(x):
         q = torch.empty(x.shape[0], n_heads, head_dim, dtype=x.dtype, device=x.device)
         native().skinny_gemm_rope(q, x, Ws, pro, positions, cos_sin, k_cache, v_cache, slots, n_heads, n_kv_heads,

@@ -228,6 +228,35 @@ def fold_gamma(W, gamma=None, rope_heads: int = 0, head_dim: int = 0):
     return out
 
 
+FP8_MAX = 448.0   # largest finite OCP e4m3fn value
+
+
+def quantize_fp8(W, gamma=None, rope_heads: int = 0, head_dim: int = 0):
+    """The fp8 weight-only contract (csrc/gemm_skinny_fp8.hip): row-major e4m3fn codes (uint8) and
+    one fp32 scale per row of ``wf = fp32(W) * fp32(gamma)`` (no bf16 rounding of the fold):
+    ``scale = amax / 448`` (1 for an all-zero row), ``code = e4m3_rne(clamp(wf * (448 / amax),
+    +-448))``. The clamp matters: torch's cast gives NaN, not 448, above 464. Rows (and scales)
+    permuted for the ROPE epilogue as :func:`fold_gamma`."""
+    wf = W.float() if gamma is None else W.float() * gamma.float()[None, :]
+    amax = wf.abs().amax(dim=1)
+    nz = amax > 0
+    # (tensor / tensor: ``448.0 / amax`` would be reciprocal(amax) * 448, two roundings)
+    inv = torch.where(nz, torch.full_like(amax, FP8_MAX) / amax, torch.ones_like(amax))
+    scale = torch.where(nz, amax / FP8_MAX, torch.ones_like(amax))
+    y = (wf * inv[:, None]).clamp(-FP8_MAX, FP8_MAX)
+    codes = y.to(torch.float8_e4m3fn).view(torch.uint8)
+    if rope_heads:
+        perm = rope_row_perm(W.shape[0], rope_heads, head_dim).to(W.device)
+        codes, scale = codes[perm].contiguous(), scale[perm].contiguous()
+    return codes, scale
+
+
+def dequantize_fp8(codes, scale):
+    """``bf16(code * scale)`` of row-major codes, rows as stored: the weight every fp8 GEMM path
+    (fused decode, unfused, prefill) computes with."""
+    return (codes.view(torch.float8_e4m3fn).float() * scale.float()[:, None]).to(torch.bfloat16)
+
+
 def skinny_gemm(x, Wf, pro=0, epi=0, res=None, eps=1e-5, x2=None, xout=None):
     """Semantics of csrc/gemm_skinny.hip on the (gamma-folded, row-major) weight ``Wf``:
     y = rsqrt(mean(x^2) + eps)[:, None] * (x @ Wf^T) for the NORM prologue; NORM_ADD (pro=2)

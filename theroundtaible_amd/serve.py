@@ -798,7 +798,8 @@ class RoundtableServer:
 def build_server(model: str, weights: str = "random:0", device: str = "cuda:0", dtype: str = "bf16",
                  host: str = "127.0.0.1", port: int = 8000, max_batch: int = 16, max_tokens: int = 512,
                  use_graphs: bool = True, num_blocks: Optional[int] = None,
-                 tp: int = 1, op_limit_s: float = 660.0) -> Optional[RoundtableServer]:
+                 tp: int = 1, op_limit_s: float = 660.0,
+                 weight_quant: Optional[str] = None) -> Optional[RoundtableServer]:
     """The server (rank 0), or — on a follower rank of a ``tp > 1`` launch — None after that
     rank has served rank 0's operations until shutdown."""
     # a checkpoint directory defines the architecture: preset + shape overrides from config.json
@@ -825,7 +826,8 @@ def build_server(model: str, weights: str = "random:0", device: str = "cuda:0", 
         if device != "cpu":
             device = cluster.device
     ecfg = EngineConfig(model=model, weights=weights, device=device, dtype=dtype, use_graphs=use_graphs,
-                        max_batch=max_batch, num_blocks=num_blocks, model_overrides=overrides)
+                        max_batch=max_batch, num_blocks=num_blocks, model_overrides=overrides,
+                        weight_quant=weight_quant)
     if ecfg.device == "cpu":
         ecfg.dtype = "fp32" if dtype == "bf16" else dtype
         ecfg.use_graphs = False
