@@ -397,6 +397,66 @@ std::pair<const void*, void*> add_operands(const torch::Tensor& x, int64_t pro, 
   return {x2->data_ptr(), xo};
 }
 
+// ---- argument checks shared by the bf16 and fp8 decode GEMM entry points ----------------------
+// out / res / ldo of a GEMM whose weight has `rows` rows: N = rows (SwiGLU: rows / 2) output
+// columns; RESID accumulates into res (no out), every other epilogue writes out [M, N]
+struct GemmOut {
+  void* out;
+  void* res;
+  int64_t N, ldo;
+};
+GemmOut gemm_out(const char* who, const torch::Tensor& out, const c10::optional<torch::Tensor>& res, int64_t M,
+                 int64_t rows, int64_t epi) {
+  int64_t N = rows;
+  if (epi == 2) {
+    TORCH_CHECK(N % 32 == 0, "swiglu W must stack [gate; up]");
+    N /= 2;
+  }
+  TORCH_CHECK(N % 16 == 0, who, ": N must be a multiple of 16");
+  if (epi == 1) {
+    TORCH_CHECK(res.has_value(), "resid epilogue needs res");
+    check_bf16(*res, "res");
+    TORCH_CHECK(res->dim() == 2 && res->size(0) == M && res->size(1) == N, "resid epilogue shapes");
+    return {nullptr, res->data_ptr(), N, N};
+  }
+  check_bf16(out, "out");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == M && out.size(1) == N, "out must be [M, N]");
+  return {out.data_ptr(), nullptr, N, out.stride(0)};
+}
+// split-K / CU-balanced launch workspace (counters zero between calls)
+std::pair<int*, int64_t> split_workspace(const c10::optional<torch::Tensor>& split_ws, const torch::Tensor& x) {
+  if (!split_ws.has_value()) return {nullptr, 0};
+  TORCH_CHECK(split_ws->scalar_type() == torch::kInt32 && split_ws->is_contiguous() &&
+                  split_ws->device() == x.device(), "split_ws: contiguous int32 on x's device");
+  return {split_ws->data_ptr<int>(), split_ws->numel()};
+}
+// operands of the ROPE epilogue; returns the bias pointer (fp32, already in the epilogue's column
+// order: ops.rope_bias) or null
+const float* rope_operands(const char* who, const torch::Tensor& q_out, const torch::Tensor& x, int64_t M,
+                           const torch::Tensor& positions, const torch::Tensor& cos_sin, const torch::Tensor& k_cache,
+                           const torch::Tensor& v_cache, const torch::Tensor& slots, int64_t Hq, int64_t Hkv, int64_t D,
+                           const c10::optional<torch::Tensor>& bias) {
+  TORCH_CHECK(q_out.numel() == M * Hq * D, "q_out must be [M, Hq, D]");
+  check_type(positions, torch::kInt64, "positions");
+  check_type(slots, torch::kInt64, "slots");
+  check_type(cos_sin, torch::kFloat32, "cos_sin");
+  TORCH_CHECK(positions.numel() >= M && slots.numel() >= M, "positions/slots must cover M rows");
+  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == D, "cos_sin must be [max_pos, D]");
+  check_caches(k_cache, v_cache, Hkv, D);
+  if (!bias.has_value()) return nullptr;
+  TORCH_CHECK(bias->scalar_type() == torch::kFloat32 && bias->is_contiguous() &&
+                  bias->numel() == (Hq + 2 * Hkv) * D && bias->device() == x.device(),
+              who, ": bias must be contiguous fp32 [N] on x's device");
+  return bias->data_ptr<float>();
+}
+void check_fp8_weight(const torch::Tensor& Wq, const torch::Tensor& scale, int64_t rows, int64_t K, const char* who) {
+  check_type(Wq, torch::kUInt8, "Wq");
+  check_type(scale, torch::kFloat32, "wscale");
+  TORCH_CHECK(Wq.dim() == 2 && Wq.size(0) == rows && Wq.size(1) == K, who, ": Wq must be uint8 [N, K]");
+  TORCH_CHECK(scale.numel() == rows, who, ": wscale must have one entry per weight row");
+  TORCH_CHECK(K % 64 == 0 && rows % 16 == 0, who, ": fp8 weights need K % 64 == 0 and N % 16 == 0");
+}
+
 void skinny_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor Ws, int64_t pro, int64_t epi,
                  c10::optional<torch::Tensor> res, double eps, c10::optional<torch::Tensor> x2,
                  c10::optional<torch::Tensor> xout, c10::optional<torch::Tensor> split_ws, int64_t split_mode) {
@@ -406,36 +466,12 @@ void skinny_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor Ws, int64_t p
   const int64_t M = x.size(0), K = x.size(1);
   TORCH_CHECK(M >= 1 && M <= 32, "skinny_gemm: 1 <= M <= 32");
   TORCH_CHECK(K % 32 == 0, "skinny_gemm: K must be a multiple of 32");
-  int64_t N = Ws.size(0);
-  if (epi == 2) {
-    TORCH_CHECK(N % 32 == 0, "swiglu W must stack [gate; up]");
-    N /= 2;
-  }
-  TORCH_CHECK(N % 16 == 0, "skinny_gemm: N must be a multiple of 16");
-  void* rp = nullptr;
-  int64_t ldo = N;
-  if (epi == 1) {
-    TORCH_CHECK(res.has_value(), "resid epilogue needs res");
-    check_bf16(*res, "res");
-    TORCH_CHECK(res->dim() == 2 && res->size(0) == M && res->size(1) == N, "resid epilogue shapes");
-    rp = res->data_ptr();
-  } else {
-    check_bf16(out, "out");
-    TORCH_CHECK(out.dim() == 2 && out.size(0) == M && out.size(1) == N, "out must be [M, N]");
-    ldo = out.stride(0);
-  }
+  const GemmOut o = gemm_out("skinny_gemm", out, res, M, Ws.size(0), epi);
   const auto addo = add_operands(x, pro, x2, xout);
-  int* sw = nullptr;
-  int64_t sw_n = 0;
-  if (split_ws.has_value()) {   // split-K / CU-balanced launch workspace (counters zero between calls)
-    TORCH_CHECK(split_ws->scalar_type() == torch::kInt32 && split_ws->is_contiguous() &&
-                    split_ws->device() == x.device(), "split_ws: contiguous int32 on x's device");
-    sw = split_ws->data_ptr<int>();
-    sw_n = split_ws->numel();
-  }
-  const int rc = launch_skinny_gemm(epi == 1 ? nullptr : out.data_ptr(), x.data_ptr(), Ws.data_ptr(), rp, (int)M,
-                                    (int)N, (int)K, (int)ldo, (float)eps, (int)pro, (int)epi, nullptr, addo.first,
-                                    addo.second, cur_stream(), sw, sw_n, (int)split_mode);
+  const auto sw = split_workspace(split_ws, x);
+  const int rc = launch_skinny_gemm(o.out, x.data_ptr(), Ws.data_ptr(), o.res, (int)M, (int)o.N, (int)K, (int)o.ldo,
+                                    (float)eps, (int)pro, (int)epi, nullptr, addo.first, addo.second, cur_stream(),
+                                    sw.first, sw.second, (int)split_mode);
   TORCH_CHECK(rc == 0, "skinny_gemm: unsupported configuration (rc=", rc, ")");
 }
 
@@ -452,31 +488,15 @@ void skinny_gemm_rope(torch::Tensor q_out, torch::Tensor x, torch::Tensor Ws, in
   const int64_t M = x.size(0), K = x.size(1);
   TORCH_CHECK(M >= 1 && M <= 32 && K % 32 == 0, "skinny_gemm_rope: 1 <= M <= 32, K % 32 == 0");
   TORCH_CHECK(Ws.size(0) == (Hq + 2 * Hkv) * D && D % 16 == 0, "skinny_gemm_rope: Ws must be [(Hq+2Hkv)*D, K]");
-  TORCH_CHECK(q_out.numel() == M * Hq * D, "q_out must be [M, Hq, D]");
-  check_type(positions, torch::kInt64, "positions");
-  check_type(slots, torch::kInt64, "slots");
-  check_type(cos_sin, torch::kFloat32, "cos_sin");
-  TORCH_CHECK(positions.numel() >= M && slots.numel() >= M, "positions/slots must cover M rows");
-  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == D, "cos_sin must be [max_pos, D]");
-  check_caches(k_cache, v_cache, Hkv, D);
-  if (bias.has_value())   // fp32, already in the ROPE epilogue's column order (ops.rope_bias)
-    TORCH_CHECK(bias->scalar_type() == torch::kFloat32 && bias->is_contiguous() && bias->numel() == Ws.size(0) &&
-                    bias->device() == x.device(), "skinny_gemm_rope: bias must be contiguous fp32 [N] on x's device");
+  const float* bp = rope_operands("skinny_gemm_rope", q_out, x, M, positions, cos_sin, k_cache, v_cache, slots, Hq,
+                                  Hkv, D, bias);
   const auto addo = add_operands(x, pro, x2, xout);
-  int* sw = nullptr;
-  int64_t sw_n = 0;
-  if (split_ws.has_value()) {   // split-K / CU-balanced launch workspace (counters zero between calls)
-    TORCH_CHECK(split_ws->scalar_type() == torch::kInt32 && split_ws->is_contiguous() &&
-                    split_ws->device() == x.device(), "split_ws: contiguous int32 on x's device");
-    sw = split_ws->data_ptr<int>();
-    sw_n = split_ws->numel();
-  }
+  const auto sw = split_workspace(split_ws, x);
   const int rc = launch_skinny_gemm_rope(q_out.data_ptr(), x.data_ptr(), Ws.data_ptr(), (int)M, (int)K, (int)pro,
                                          (float)eps, positions.data_ptr<int64_t>(), cos_sin.data_ptr<float>(),
                                          k_cache.data_ptr(), v_cache.data_ptr(), slots.data_ptr<int64_t>(), (int)Hq,
                                          (int)Hkv, (int)D, (int)k_cache.size(2), addo.first, addo.second,
-                                         cur_stream(), sw, sw_n, (int)split_mode,
-                                         bias.has_value() ? bias->data_ptr<float>() : nullptr);
+                                         cur_stream(), sw.first, sw.second, (int)split_mode, bp);
   TORCH_CHECK(rc == 0, "skinny_gemm_rope: unsupported configuration (rc=", rc, ")");
 }
 
@@ -683,14 +703,7 @@ void kv_block_copy(torch::Tensor k, torch::Tensor v, torch::Tensor src, torch::T
   TORCH_CHECK(rc == 0, "kv_block_copy: unsupported configuration (rc=", rc, ")");
 }
 
-// ---- FP8 weight-only decode GEMMs (csrc/gemm_skinny_fp8.hip) --------------------------------
-void check_fp8_weight(const torch::Tensor& Wq, const torch::Tensor& scale, int64_t rows, int64_t K, const char* who) {
-  check_type(Wq, torch::kUInt8, "Wq");
-  check_type(scale, torch::kFloat32, "wscale");
-  TORCH_CHECK(Wq.dim() == 2 && Wq.size(0) == rows && Wq.size(1) == K, who, ": Wq must be uint8 [N, K]");
-  TORCH_CHECK(scale.numel() == rows, who, ": wscale must have one entry per weight row");
-  TORCH_CHECK(K % 64 == 0 && rows % 16 == 0, who, ": fp8 weights need K % 64 == 0 and N % 16 == 0");
-}
+// ---- FP8 weight-only decode GEMMs (quantiser: csrc/gemm_skinny_fp8.hip, launches: gemm_skinny.hip) ----
 void shuffle_weight_fp8(torch::Tensor Wq, torch::Tensor scale, torch::Tensor W, c10::optional<torch::Tensor> gamma,
                         int64_t rope_heads, int64_t head_dim, bool swiglu) {
   check_bf16(W, "W");
@@ -728,26 +741,10 @@ void skinny_gemm_fp8(torch::Tensor out, torch::Tensor x, torch::Tensor Wq, torch
   TORCH_CHECK(M >= 1 && M <= 16, "skinny_gemm_fp8: 1 <= M <= 16");
   TORCH_CHECK(pro == 0 || pro == 1, "skinny_gemm_fp8: prologue PLAIN or NORM");
   TORCH_CHECK(epi >= 0 && epi <= 2, "skinny_gemm_fp8: epilogue STORE, RESID or SWIGLU");
-  int64_t N = Wq.size(0);
-  if (epi == 2) {
-    TORCH_CHECK(N % 32 == 0, "swiglu W must stack [gate; up]");
-    N /= 2;
-  }
-  void* rp = nullptr;
-  int64_t ldo = N;
-  if (epi == 1) {
-    TORCH_CHECK(res.has_value(), "resid epilogue needs res");
-    check_bf16(*res, "res");
-    TORCH_CHECK(res->dim() == 2 && res->size(0) == M && res->size(1) == N, "resid epilogue shapes");
-    rp = res->data_ptr();
-  } else {
-    check_bf16(out, "out");
-    TORCH_CHECK(out.dim() == 2 && out.size(0) == M && out.size(1) == N, "out must be [M, N]");
-    ldo = out.stride(0);
-  }
-  const int rc = launch_skinny_gemm_fp8(epi == 1 ? nullptr : out.data_ptr(), x.data_ptr(), Wq.data_ptr(),
-                                        scale.data_ptr<float>(), rp, (int)M, (int)N, (int)K, (int)ldo, (float)eps,
-                                        (int)pro, (int)epi, nullptr, cur_stream());
+  const GemmOut o = gemm_out("skinny_gemm_fp8", out, res, M, Wq.size(0), epi);
+  const int rc = launch_skinny_gemm_fp8(o.out, x.data_ptr(), Wq.data_ptr(), scale.data_ptr<float>(), o.res, (int)M,
+                                        (int)o.N, (int)K, (int)o.ldo, (float)eps, (int)pro, (int)epi, nullptr,
+                                        cur_stream());
   TORCH_CHECK(rc == 0, "skinny_gemm_fp8: unsupported configuration (rc=", rc, ")");
 }
 void skinny_gemm_rope_fp8(torch::Tensor q_out, torch::Tensor x, torch::Tensor Wq, torch::Tensor scale, int64_t pro,
@@ -761,22 +758,13 @@ void skinny_gemm_rope_fp8(torch::Tensor q_out, torch::Tensor x, torch::Tensor Wq
   check_fp8_weight(Wq, scale, (Hq + 2 * Hkv) * D, K, "skinny_gemm_rope_fp8");
   TORCH_CHECK(M >= 1 && M <= 16 && D % 16 == 0, "skinny_gemm_rope_fp8: 1 <= M <= 16, D % 16 == 0");
   TORCH_CHECK(pro == 0 || pro == 1, "skinny_gemm_rope_fp8: prologue PLAIN or NORM");
-  TORCH_CHECK(q_out.numel() == M * Hq * D, "q_out must be [M, Hq, D]");
-  check_type(positions, torch::kInt64, "positions");
-  check_type(slots, torch::kInt64, "slots");
-  check_type(cos_sin, torch::kFloat32, "cos_sin");
-  TORCH_CHECK(positions.numel() >= M && slots.numel() >= M, "positions/slots must cover M rows");
-  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == D, "cos_sin must be [max_pos, D]");
-  check_caches(k_cache, v_cache, Hkv, D);
-  if (bias.has_value())
-    TORCH_CHECK(bias->scalar_type() == torch::kFloat32 && bias->is_contiguous() && bias->numel() == Wq.size(0) &&
-                    bias->device() == x.device(), "skinny_gemm_rope_fp8: bias must be contiguous fp32 [N] on x's device");
+  const float* bp = rope_operands("skinny_gemm_rope_fp8", q_out, x, M, positions, cos_sin, k_cache, v_cache, slots,
+                                  Hq, Hkv, D, bias);
   const int rc = launch_skinny_gemm_rope_fp8(q_out.data_ptr(), x.data_ptr(), Wq.data_ptr(), scale.data_ptr<float>(),
                                              (int)M, (int)K, (int)pro, (float)eps, positions.data_ptr<int64_t>(),
                                              cos_sin.data_ptr<float>(), k_cache.data_ptr(), v_cache.data_ptr(),
                                              slots.data_ptr<int64_t>(), (int)Hq, (int)Hkv, (int)D,
-                                             (int)k_cache.size(2), bias.has_value() ? bias->data_ptr<float>() : nullptr,
-                                             cur_stream());
+                                             (int)k_cache.size(2), bp, cur_stream());
   TORCH_CHECK(rc == 0, "skinny_gemm_rope_fp8: unsupported configuration (rc=", rc, ")");
 }
 }  // namespace

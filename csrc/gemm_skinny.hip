@@ -1,8 +1,10 @@
 // Decode-path linear layers (M <= 16 rows, up to 32 with plain / norm prologues): y[M,N] = x[M,K] . W[N,K]^T on MFMA, with the
 // layer's elementwise work fused in, so a decode layer needs no separate norm/act kernels.
 // The tile code (weight layout, pipeline, prologues, epilogues) lives in skinny_core.h and is
-// shared with the persistent decode-layer kernel; this file holds the one-tile-per-workgroup
-// launches, the weight shuffle, and the launchers.
+// shared with the persistent decode-layer kernel; the launch decision (form, variant, geometry)
+// is the pure plan_skinny_gemm of skinny_plan.h. This file holds the kernel wrappers of every
+// form, the (pro, epi) / variant dispatch, the bf16 weight shuffle, and the launchers of both
+// weight types (the fp8 quantiser is gemm_skinny_fp8.hip).
 //
 // Fusions (details in skinny_core.h):
 //   prologue NORM : RMSNorm with gamma folded into W and 1/rms(x_m) from the same A fragments
@@ -16,27 +18,28 @@
 //                   the epilogue rotates them (fp32 cos|sin table), writes q to [M, Hq, D] and
 //                   scatters k / v straight into the paged caches (k [blk][h][off][D], v
 //                   transposed [blk][h][D][off]). Replaces the K2 rope/cache launch.
-#include "skinny_core.h"
+#include "skinny_plan.h"
 
-#include <cstdio>
-#include <cstdlib>
+#include <type_traits>
+#include <utility>
 
 namespace {
 using rt::short8;
 using namespace skinny;
 
-template <int PRO, int EPI, int NW, int U>
+// one tile per workgroup; WT_FP8: e4m3 weight codes, dequantised in registers (skinny_core.h)
+template <int PRO, int EPI, int NW, int U, int WT = WT_BF16>
 __global__ void __launch_bounds__(NW * 64) skinny_gemm_kernel(GemmArgs p) {
   __shared__ GemmSmem<nacc<EPI>(), NW> sm;
-  Stage<PRO, EPI, U> st0;
-  gemm_tile<PRO, EPI, NW, U, false>(p, blockIdx.x, sm, st0, false, blockIdx.x == 0);
+  Stage<PRO, EPI, U, WT> st0;
+  gemm_tile<PRO, EPI, NW, U, false, false, -1, WT>(p, blockIdx.x, sm, st0, false, blockIdx.x == 0);
 }
 
 // TN tiles per workgroup (skinny_core.h gemm_tiles): serving batches, M > 4
 template <int PRO, int EPI, int NW, int U, int TN, int MB = 1>
 __global__ void __launch_bounds__(NW * 64) skinny_gemm_multi_kernel(GemmArgs p) {
   // two row blocks x (gate + up) x 4 tiles would not fit the static LDS: that variant is never
-  // launched (the dispatcher caps SwiGLU at 2 tiles with two row blocks), compiled as 2 tiles
+  // launched (the plan caps SwiGLU at 2 tiles with two row blocks), compiled as 2 tiles
   constexpr int TNX = (MB == 2 && nacc<EPI>() == 2 && TN > 2) ? 2 : TN;
   __shared__ GemmSmemN<nacc<EPI>(), NW, TNX, MB> sm;
   gemm_tiles<PRO, EPI, NW, U, TNX, MB>(p, blockIdx.x * TNX, sm);
@@ -67,7 +70,6 @@ __global__ void __launch_bounds__(NW * 64) skinny_gemm_alds_kernel(GemmArgs p) {
 // hand-offs finish under the whole tiles' streams), [2R, T + R) the whole tiles.
 // tools/exp_balance.hip: swiglu 768 / 896 / 1024 tiles = 31.0 / 37.6 / 40.5 us (896 is 1.8 us
 // above the line through its neighbours).
-constexpr int SPLIT_CTRS = 256;   // counter words at the head of the split workspace
 template <int PRO, int EPI, int NW, int U>
 __global__ void __launch_bounds__(NW * 64) skinny_gemm_bal_kernel(GemmArgs p, int* __restrict__ ws, int R, int xpair) {
   __shared__ GemmSmem<nacc<EPI>(), NW> sm;
@@ -157,428 +159,151 @@ int device_cus() {
   return cache[dev] > 0 ? cache[dev] : 0;
 }
 
-// RT_WEIGHT_ORDER=0 pins tile-major weights everywhere (A/B against the shape rule; read once,
-// so shuffle and GEMM launches of one process agree)
-int forced_order() {
-  static const int v = [] {
-    const char* e = getenv("RT_WEIGHT_ORDER");
-    return e ? atoi(e) : -1;
-  }();
-  return v;
+// Runtime (pro, epi) -> compile-time constants: f(integral_constant PRO, integral_constant EPI)
+// runs for the pair if FORM launches it. A pair outside allowed(FORM, WT, ..) is not instantiated
+// and returns -2.
+template <int FORM, int WT, class F, int... I>
+int with_pro_epi(int pro, int epi, F&& f, std::integer_sequence<int, I...>) {
+  int rc = -2;
+  ([&] {
+    constexpr int P = I / 4, E = I % 4;
+    if constexpr (allowed(FORM, WT, P, E))
+      if (pro == P && epi == E) rc = f(std::integral_constant<int, P>{}, std::integral_constant<int, E>{});
+  }(), ...);
+  return rc;
+}
+template <int FORM, int WT, class F>
+int with_pro_epi(int pro, int epi, F&& f) {
+  return with_pro_epi<FORM, WT>(pro, epi, f, std::make_integer_sequence<int, 12>{});   // 3 prologues x 4 epilogues
 }
 
-// Ws[t][s][l][j] = W[16t + (l&15)][32s + 8(l>>4) + j] (optionally W * gamma[k] folded in)
-// If rope_rows > 0, output row r < rope_rows takes source row h*D + (p>>1) + (p&1)*D/2
-// (r = h*D + p): the pair-interleaved q/k order the ROPE epilogue expects.
-// swiglu: N = 2I rows [gate; up], stored k-step-paired: Ws[t][s][h][l][j] = W[h*I + 16t + (l&15)][...]
-__global__ void shuffle_kernel(short8* __restrict__ Ws, const uint16_t* __restrict__ W,
-                               const uint16_t* __restrict__ gamma, int N, int K, int rope_rows, int D, int swiglu,
-                               int force_order) {
-  const int nsteps = K / 32;
-  const int64_t total = (int64_t)(N / 16) * nsteps * 64;
-  const int T = swiglu ? N / 32 : N / 16;   // output tiles (SwiGLU: gate + up rows per tile)
-  const int order = force_order >= 0 ? force_order : weight_order(T, nsteps, swiglu != 0, rope_rows > 0);
-  const int recs = swiglu ? 128 : 64;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int l = (int)(i & 63);
-    int64_t ts = i >> 6;
-    int h = 0;
-    if (swiglu) {
-      h = (int)(ts & 1);
-      ts >>= 1;
-    }
-    const int s = (int)(ts % nsteps);
-    const int64_t t = ts / nsteps;
-    int row = (int)(16 * t + (l & 15)) + h * (N / 2);
-    if (row < rope_rows) {
-      const int h = row / D, p = row - h * D;
-      row = h * D + (p >> 1) + (p & 1) * (D >> 1);
-    }
-    const int k0 = 32 * s + 8 * (l >> 4);
-    short8 v = *reinterpret_cast<const short8*>(W + (size_t)row * K + k0);
-    if (gamma != nullptr) {
-      const short8 gv = *reinterpret_cast<const short8*>(gamma + k0);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = (short)rt::f2bf(rt::bf2f((uint16_t)v[j]) * rt::bf2f((uint16_t)gv[j]));
-    }
-    Ws[rec_index((int)t, s, T, nsteps, order, recs) + h * 64 + l] = v;
+// The same for the plan's (NW, U, TN, MB): each form lists the variants it is compiled with
+template <int NW_, int U_, int TN_ = 1, int MB_ = 1>
+struct V {
+  static constexpr int NW = NW_, U = U_, TN = TN_, MB = MB_;
+};
+template <class... Vs, class F>
+int with_variant(const SkinnyPlan& pl, F&& f) {
+  int rc = -2;
+  ((pl.NW == Vs::NW && pl.U == Vs::U && pl.TN == Vs::TN && pl.MB == Vs::MB ? void(rc = f(Vs{})) : void()), ...);
+  return rc;
+}
+
+template <class... P, class... A>
+int launch(void (*kernel)(P...), const SkinnyPlan& pl, hipStream_t stream, A... args) {
+  hipLaunchKernelGGL(kernel, dim3(pl.grid), dim3(pl.block), pl.lds_bytes, stream, args...);
+  return hipGetLastError() == hipSuccess ? 0 : -6;
+}
+
+template <int WT>
+int launch_plan(const SkinnyPlan& pl, const GemmArgs& args, int pro, int epi, int* ws, hipStream_t stream) {
+  switch (pl.form) {
+    case ONE_TILE:
+      return with_pro_epi<ONE_TILE, WT>(pro, epi, [&](auto P, auto E) {
+        const auto go = [&](auto v) { return launch(skinny_gemm_kernel<P(), E(), v.NW, v.U, WT>, pl, stream, args); };
+        if constexpr (WT == WT_FP8)
+          return with_variant<V<4, 2>, V<4, 4>>(pl, go);
+        else
+          return with_variant<V<4, 2>, V<16, 2>, V<8, 2>, V<4, 8>, V<8, 4>, V<8, 8>, V<4, 4>>(pl, go);
+      });
+    case ALDS:
+      return with_pro_epi<ALDS, WT>(pro, epi, [&](auto P, auto E) {
+        return with_variant<V<4, 2>, V<16, 2>, V<8, 2>, V<4, 8>, V<8, 4>, V<8, 8>, V<4, 4>>(
+            pl, [&](auto v) { return launch(skinny_gemm_alds_kernel<P(), E(), v.NW, v.U>, pl, stream, args); });
+      });
+    case SPLITK:
+      return with_pro_epi<SPLITK, WT>(pro, epi, [&](auto P, auto E) {
+        if (pl.alds) return launch(skinny_gemm_splitk_kernel<P(), E(), 8, 2, true>, pl, stream, args, ws, pl.S);
+        return with_variant<V<4, 2>, V<4, 4>, V<8, 2>>(
+            pl, [&](auto v) { return launch(skinny_gemm_splitk_kernel<P(), E(), v.NW, v.U>, pl, stream, args, ws, pl.S); });
+      });
+    case MULTI:
+      return with_pro_epi<MULTI, WT>(pro, epi, [&](auto P, auto E) {
+        return with_variant<V<4, 2, 4, 2>, V<4, 2, 2, 2>, V<4, 2, 1, 2>, V<8, 2, 2>, V<4, 4, 2>, V<4, 2, 2>, V<8, 2, 4>,
+                            V<4, 2, 4>>(pl, [&](auto v) {
+          return launch(skinny_gemm_multi_kernel<P(), E(), v.NW, v.U, v.TN, v.MB>, pl, stream, args);
+        });
+      });
+    case MULTI_SPLIT:
+      return with_pro_epi<MULTI_SPLIT, WT>(pro, epi, [&](auto P, auto E) {
+        return with_variant<V<4, 2, 2, 2>, V<4, 2, 2>>(pl, [&](auto v) {
+          return launch(skinny_gemm_multi_split_kernel<P(), E(), v.NW, v.U, 2, v.MB>, pl, stream, args, ws, pl.S);
+        });
+      });
+    case BALANCED:
+      return with_pro_epi<BALANCED, WT>(pro, epi, [&](auto P, auto E) {
+        return launch(skinny_gemm_bal_kernel<P(), E(), 4, 2>, pl, stream, args, ws, pl.R, pl.xpair);
+      });
   }
+  return -2;
 }
 
-// Exact inverse of shuffle_kernel's permutation (gamma, if any, stays folded): the row-major
-// weight for the prefill GEMMs when only the shuffled copy is kept resident (70B on one GPU).
-__global__ void unshuffle_kernel(uint16_t* __restrict__ W, const short8* __restrict__ Ws, int N, int K, int rope_rows,
-                                 int D, int swiglu, int force_order) {
-  const int nsteps = K / 32;
-  const int64_t total = (int64_t)(N / 16) * nsteps * 64;
-  const int T = swiglu ? N / 32 : N / 16;
-  const int order = force_order >= 0 ? force_order : weight_order(T, nsteps, swiglu != 0, rope_rows > 0);
-  const int recs = swiglu ? 128 : 64;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int l = (int)(i & 63);
-    int64_t ts = i >> 6;
-    int h = 0;
-    if (swiglu) {
-      h = (int)(ts & 1);
-      ts >>= 1;
-    }
-    const int s = (int)(ts % nsteps);
-    const int64_t t = ts / nsteps;
-    int row = (int)(16 * t + (l & 15)) + h * (N / 2);
-    if (row < rope_rows) {
-      const int hh = row / D, p = row - hh * D;
-      row = hh * D + (p >> 1) + (p & 1) * (D >> 1);
-    }
-    const int k0 = 32 * s + 8 * (l >> 4);
-    *reinterpret_cast<short8*>(W + (size_t)row * K + k0) = Ws[rec_index((int)t, s, T, nsteps, order, recs) + h * 64 + l];
-  }
-}
-}  // namespace
-
-int launch_unshuffle_weight(void* W, const void* Ws, int N, int K, int rope_rows, int D, int swiglu,
-                            hipStream_t stream) {
-  if (N % 16 || K % 32 || N <= 0 || K <= 0 || rope_rows > N || (rope_rows && (D <= 0 || D % 2)) ||
-      (swiglu && (N / 2) % 16))
+// validate -> plan -> fill GemmArgs -> one dispatch on the plan's form. WT_FP8: Ws holds fp8 weight
+// codes and wscale their per-row scales (M <= 16, K % 64 == 0); N = output columns (SwiGLU: I).
+int launch_gemm(int wt, void* out, const void* x, const void* Ws, const float* wscale, void* res, int M, int N, int K,
+                int ldo, float eps, int pro, int epi, const void* rope, const void* x2, void* xo, hipStream_t stream,
+                int* split_ws, int64_t split_ws_ints, int split_mode) {
+  const bool f8 = wt == WT_FP8;
+  if (!f8 && pro == PRO_NORM_ADD && x2 == nullptr) return -5;
+  // 17..32 rows: only the multi-tile launches (two 16-row blocks per MFMA pass)
+  if (M < 1 || M > (f8 ? 16 : 32) || K <= 0 || N <= 0 || K % (f8 ? 64 : 32) || N % 16 || (f8 && wscale == nullptr))
     return -1;
-  const int64_t total = (int64_t)(N / 16) * (K / 32) * 64;
-  const int64_t grid = (total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536;
-  hipLaunchKernelGGL(unshuffle_kernel, dim3((unsigned)grid), dim3(256), 0, stream, (uint16_t*)W, (const short8*)Ws,
-                     N, K, rope_rows, D, swiglu, forced_order());
-  return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-// ALDS decision (skinny_core.h): RT_GEMM_ALDS=1 whenever the staged rows fit, =2 when they fit
-// and the launch has at most one workgroup per CU, unset / 0 never. Staged rows + row sums
-// <= 48 KB, so the workgroup stays under 64 KB of LDS.
-constexpr int ALDS_MAX_BYTES = 48 * 1024;
-bool use_alds(int M, int kspan, int wgs, int cus) {
-  // default OFF: measured slower than the pipelined activation loads on every shard shape except
-  // the NORM_ADD prologue, which the decode path no longer uses (tools/probes/gemm_variants.py,
-  // profiles/r04/gemm_variants.md); RT_GEMM_ALDS=1 forces it, =2 is the "shard shapes" rule
-  static const int mode = [] {
-    const char* e = getenv("RT_GEMM_ALDS");
-    return e ? atoi(e) : 0;
-  }();
-  if (mode == 0 || skinny::alds_bytes(M, kspan) > ALDS_MAX_BYTES) return false;
-  return mode == 1 || (mode == 2 && cus > 0 && wgs <= cus);
-}
-
-int split_workspace_ints(int max_split_tiles) { return SPLIT_CTRS + max_split_tiles * 2 * SPLIT_STRIDE; }
-
-// Split-K part count for a T-tile, ks-k-step GEMM on `cus` CUs (0 = no split-K): the most parts
-// that keep every CU at one workgroup (profiles/r03/gemm_tp_shards_*), each part >= 8 k-steps,
-// T x S capped by the workspace. RT_SPLITK=<S> pins S (1 = off),
-// RT_SPLITK_TARGET=<wgs> = the r03-first rule S = ceil(wgs / T) (microbenchmark sweeps; read once).
-int splitk_parts(int T, int ks, int cus, int64_t ws_ints) {
-  static const int pinned = [] {
-    const char* e = getenv("RT_SPLITK");
-    return e ? atoi(e) : 0;
-  }();
-  static const int target_env = [] {
-    const char* e = getenv("RT_SPLITK_TARGET");
-    return e ? atoi(e) : 0;
-  }();
-  if (cus <= 0 || T >= cus || T > SPLIT_CTRS || pinned == 1) return 0;
-  const int smax = ks / 8 < 16 ? ks / 8 : 16;
-  int S;
-  if (pinned > 1) {
-    S = pinned;
-  } else if (target_env > 0) {
-    S = (target_env + T - 1) / T;
-  } else {
-    // at most ONE part per CU: T x S just above the CU count doubles some CUs, which costs more
-    // than the split gains (r03 microbench, Llama-3-8B shards, us unsplit -> split: tp 8 qkv 48
-    // tiles 8.70 -> 8.34 at S = 6 (288 WGs) / 11.26 at S = 11; tp 2 qkv 192 tiles 9.44 -> 10.85 at
-    // S = 2; tp 4 gate_up 224 tiles 13.64 -> 14.18 at S = 2): S = floor(cus / T), so only shapes
-    // with <= cus / 2 tiles split
-    S = cus / T;
-  }
-  S = S < smax ? S : smax;
-  while (S >= 2 && SPLIT_CTRS + (int64_t)T * S * SPLIT_STRIDE > ws_ints) --S;
-  return S >= 2 ? S : 0;
-}
-
-int launch_skinny_gemm(void* out, const void* x, const void* Ws, void* res, int M, int N, int K, int ldo, float eps,
-                       int pro, int epi, const void* rope, const void* x2, void* xo, hipStream_t stream,
-                       int* split_ws, int64_t split_ws_ints, int split_mode) {
-  if (pro == PRO_NORM_ADD && x2 == nullptr) return -5;
-  // 17..32 rows: only the multi-tile launches below (two 16-row blocks per MFMA pass)
-  if (M < 1 || M > 32 || K % 32 || N % 16) return -1;
   if (M > 16 && (pro == PRO_NORM_ADD || epi == EPI_AR)) return -1;
+  if (f8 && pro != PRO_PLAIN && pro != PRO_NORM) return -2;   // reported ahead of a missing ROPE operand
   RopeEpi re{};
   if (epi == EPI_ROPE) {
     if (rope == nullptr) return -3;
     re = *static_cast<const RopeEpi*>(rope);
     if (re.D % 16 || N != (re.Hq + 2 * re.Hkv) * re.D) return -4;
   }
-  // split-K (split_mode bit 1) when the shape has fewer tiles than CUs: tensor-parallel shards
-  if (split_ws != nullptr && (split_mode & 2) && M <= 16) {
-    const int T = N / 16;
-    const int S = splitk_parts(T, K / 32, device_cus(), split_ws_ints);
-    if (S >= 2) {
-      GemmArgs args{(uint16_t*)out, (const uint16_t*)x, (const short8*)Ws, (uint16_t*)res, M, N, K, ldo,
-                    eps, re, (const uint16_t*)x2, (uint16_t*)xo};
-      args.kmajor = forced_order();
-      const dim3 grid(T * S);
-      const int kspan = 32 * ((K / 32 + S - 1) / S + 1);
-      const bool alds = use_alds(M, kspan, T * S, device_cus());
-      const size_t lds = alds ? (size_t)skinny::alds_bytes(M, kspan) : 0;
-      // (NW, U) of the split-K parts: 8 waves x 2 steps — one part per CU streams with twice
-      // the bytes in flight of 4 waves (r03 microbench, Llama-3-8B tp 4 qkv 8.79 -> 7.98 us; tp 2/8
-      // shards within noise; 4x4 no better: profiles/r03/gemm_tp_splitk_cfg_sweep.md).
-      // RT_SPLITK_CFG=<NW>x<U> (8x2, 4x2, 4x4) pins it
-      static const int skcfg = [] {
-        const char* e = getenv("RT_SPLITK_CFG");
-        int nw = 0, u = 0;
-        if (!e || sscanf(e, "%dx%d", &nw, &u) != 2) return 802;
-        return nw * 100 + u;
-      }();
-#define RT_SK(P, E)                                                                                                 \
-  do {                                                                                                              \
-    if (skcfg == 402)                                                                                               \
-      hipLaunchKernelGGL((skinny_gemm_splitk_kernel<P, E, 4, 2>), grid, dim3(256), 0, stream, args, split_ws, S);  \
-    else if (skcfg == 404)                                                                                          \
-      hipLaunchKernelGGL((skinny_gemm_splitk_kernel<P, E, 4, 4>), grid, dim3(256), 0, stream, args, split_ws, S);  \
-    else if (alds)                                                                                                  \
-      hipLaunchKernelGGL((skinny_gemm_splitk_kernel<P, E, 8, 2, true>), grid, dim3(512), lds, stream, args, split_ws, \
-                         S);                                                                                        \
-    else                                                                                                            \
-      hipLaunchKernelGGL((skinny_gemm_splitk_kernel<P, E, 8, 2>), grid, dim3(512), 0, stream, args, split_ws, S);  \
-  } while (0)
-      if (pro == PRO_PLAIN && epi == EPI_STORE) RT_SK(PRO_PLAIN, EPI_STORE);
-      else if (pro == PRO_NORM && epi == EPI_STORE) RT_SK(PRO_NORM, EPI_STORE);
-      else if (pro == PRO_NORM_ADD && epi == EPI_STORE) RT_SK(PRO_NORM_ADD, EPI_STORE);
-      else if (pro == PRO_PLAIN && epi == EPI_RESID) RT_SK(PRO_PLAIN, EPI_RESID);
-      else if (pro == PRO_NORM && epi == EPI_SWIGLU) RT_SK(PRO_NORM, EPI_SWIGLU);
-      else if (pro == PRO_NORM_ADD && epi == EPI_SWIGLU) RT_SK(PRO_NORM_ADD, EPI_SWIGLU);
-      else if (pro == PRO_NORM && epi == EPI_ROPE) RT_SK(PRO_NORM, EPI_ROPE);
-      else if (pro == PRO_NORM_ADD && epi == EPI_ROPE) RT_SK(PRO_NORM_ADD, EPI_ROPE);
-      else if (pro == PRO_PLAIN && epi == EPI_ROPE) RT_SK(PRO_PLAIN, EPI_ROPE);
-      else if (pro == PRO_PLAIN && epi == EPI_SWIGLU) RT_SK(PRO_PLAIN, EPI_SWIGLU);
-      else return -2;
-#undef RT_SK
-      return hipGetLastError() == hipSuccess ? 0 : -6;
-    }
-  }
-  // Serving batches (M > 4): TN tiles per workgroup share each activation fragment (skinny_core.h
-  // gemm_tiles), as long as the launch still covers 3/4 of the CUs. MI355X, Llama-3-8B, M = 16
-  // (profiles/r05/gemm_multi_tile.md): lm_head 235.0 -> 163.2 us (TN 4), gate_up 42.1 -> 38.7
-  // (TN 4), qkv 16.7 -> 13.5 (TN 2); o / down (256 tiles) lose with fewer workgroups and keep one
-  // tile. RT_SKINNY_TN=<TN> (1 = off) pins the tile count, RT_SKINNY_TNCFG=<NW>x<U> the variant
-  // (microbenchmarks); the M <= 4 decode path is unchanged.
-  // A/B knob: the smallest M the multi-tile rule applies to (M = 3 gains nothing: the activation
-  // fragments of 3 rows are L1 hits, profiles/r05/gemm_multi_tile.md); RT_SKINNY_TNS=2 forces the
-  // two-tile K-split below 9 rows
-  static const int tn_min_m = [] {
-    const char* e = getenv("RT_SKINNY_TN_MINM");
-    return e ? atoi(e) : 5;
-  }();
-  if ((M >= tn_min_m || M > 16) && (pro == PRO_PLAIN || pro == PRO_NORM) && epi != EPI_AR) {
-    const int MB = M > 16 ? 2 : 1;
-    static const int tn_env = [] {
-      const char* e = getenv("RT_SKINNY_TN");
-      return e ? atoi(e) : -1;
-    }();
-    static const int tncfg = [] {
-      const char* e = getenv("RT_SKINNY_TNCFG");
-      int nw = 0, u = 0;
-      if (!e || sscanf(e, "%dx%d", &nw, &u) != 2) return 402;
-      return nw * 100 + u;
-    }();
-    const int T16 = N / 16, cus = device_cus(), need = cus * 3 / 4;
-    int tn = tn_env >= 0 ? tn_env : (cus <= 0 ? 1 : (T16 / 4 >= need ? 4 : (T16 / 2 >= need ? 2 : 1)));
-    // LDS: two row blocks x (gate + up) x 4 tiles would not fit
-    if (MB == 2) tn = tn >= 4 && epi != EPI_SWIGLU ? 4 : (tn >= 2 ? 2 : 1);
-    // one tile per workgroup would still fill the chip (o / down: 256 tiles): two tiles per
-    // workgroup over two K halves keep the workgroup count and halve the activation reads — from
-    // 9 rows on (M = 16: down 28.8 -> 23.6 us, o 11.0 -> 10.6; M = 8: o 8.8 -> 10.0, down even,
-    // profiles/r05/gemm_multi_tile.md). RT_SKINNY_TNS=0 keeps one tile.
-    static const int tns_env = [] {
-      const char* e = getenv("RT_SKINNY_TNS");
-      return e ? atoi(e) : 1;
-    }();
-    const int G2 = (T16 + 1) / 2;
-    if (tn == 1 && tn_env < 0 && tns_env && (M > 8 || tns_env == 2) && cus > 0 && T16 >= need && G2 <= SPLIT_CTRS && K / 32 >= 32 &&
-        split_ws != nullptr && split_ws_ints >= (int64_t)SPLIT_CTRS + (int64_t)G2 * 2 * 2 * MB * SPLIT_STRIDE) {
-      GemmArgs args{(uint16_t*)out, (const uint16_t*)x, (const short8*)Ws, (uint16_t*)res, M, N, K, ldo,
-                    eps, re, nullptr, nullptr};
-      args.kmajor = forced_order();
-      const dim3 grid(G2 * 2);
-#define RT_MS(P, E)                                                                                               \
-  do {                                                                                                            \
-    if (MB == 2)                                                                                                  \
-      hipLaunchKernelGGL((skinny_gemm_multi_split_kernel<P, E, 4, 2, 2, 2>), grid, dim3(256), 0, stream, args,    \
-                         split_ws, 2);                                                                            \
-    else                                                                                                          \
-      hipLaunchKernelGGL((skinny_gemm_multi_split_kernel<P, E, 4, 2, 2>), grid, dim3(256), 0, stream, args,       \
-                         split_ws, 2);                                                                            \
-  } while (0)
-      if (pro == PRO_PLAIN && epi == EPI_STORE) RT_MS(PRO_PLAIN, EPI_STORE);
-      else if (pro == PRO_NORM && epi == EPI_STORE) RT_MS(PRO_NORM, EPI_STORE);
-      else if (pro == PRO_PLAIN && epi == EPI_RESID) RT_MS(PRO_PLAIN, EPI_RESID);
-      else if (pro == PRO_NORM && epi == EPI_RESID) RT_MS(PRO_NORM, EPI_RESID);
-      else if (pro == PRO_NORM && epi == EPI_SWIGLU) RT_MS(PRO_NORM, EPI_SWIGLU);
-      else if (pro == PRO_PLAIN && epi == EPI_SWIGLU) RT_MS(PRO_PLAIN, EPI_SWIGLU);
-      else if (pro == PRO_NORM && epi == EPI_ROPE) RT_MS(PRO_NORM, EPI_ROPE);
-      else if (pro == PRO_PLAIN && epi == EPI_ROPE) RT_MS(PRO_PLAIN, EPI_ROPE);
-      else return -2;
-#undef RT_MS
-      return hipGetLastError() == hipSuccess ? 0 : -6;
-    }
-    if (tn == 2 || tn == 4 || MB == 2) {
-      GemmArgs args{(uint16_t*)out, (const uint16_t*)x, (const short8*)Ws, (uint16_t*)res, M, N, K, ldo,
-                    eps, re, nullptr, nullptr};
-      args.kmajor = forced_order();
-      const int T = N / 16;
-      const dim3 grid((T + tn - 1) / tn);
-#define RT_MT(P, E)                                                                                               \
-  do {                                                                                                            \
-    if (MB == 2 && tn == 4)                                                                                       \
-      hipLaunchKernelGGL((skinny_gemm_multi_kernel<P, E, 4, 2, 4, 2>), grid, dim3(256), 0, stream, args);        \
-    else if (MB == 2 && tn == 2)                                                                                  \
-      hipLaunchKernelGGL((skinny_gemm_multi_kernel<P, E, 4, 2, 2, 2>), grid, dim3(256), 0, stream, args);        \
-    else if (MB == 2)                                                                                             \
-      hipLaunchKernelGGL((skinny_gemm_multi_kernel<P, E, 4, 2, 1, 2>), grid, dim3(256), 0, stream, args);        \
-    else if (tn == 2 && tncfg == 802)                                                                             \
-      hipLaunchKernelGGL((skinny_gemm_multi_kernel<P, E, 8, 2, 2>), grid, dim3(512), 0, stream, args);           \
-    else if (tn == 2 && tncfg == 404)                                                                             \
-      hipLaunchKernelGGL((skinny_gemm_multi_kernel<P, E, 4, 4, 2>), grid, dim3(256), 0, stream, args);           \
-    else if (tn == 2)                                                                                             \
-      hipLaunchKernelGGL((skinny_gemm_multi_kernel<P, E, 4, 2, 2>), grid, dim3(256), 0, stream, args);           \
-    else if (tncfg == 802)                                                                                        \
-      hipLaunchKernelGGL((skinny_gemm_multi_kernel<P, E, 8, 2, 4>), grid, dim3(512), 0, stream, args);           \
-    else                                                                                                          \
-      hipLaunchKernelGGL((skinny_gemm_multi_kernel<P, E, 4, 2, 4>), grid, dim3(256), 0, stream, args);           \
-  } while (0)
-      if (pro == PRO_PLAIN && epi == EPI_STORE) RT_MT(PRO_PLAIN, EPI_STORE);
-      else if (pro == PRO_NORM && epi == EPI_STORE) RT_MT(PRO_NORM, EPI_STORE);
-      else if (pro == PRO_PLAIN && epi == EPI_RESID) RT_MT(PRO_PLAIN, EPI_RESID);
-      else if (pro == PRO_NORM && epi == EPI_RESID) RT_MT(PRO_NORM, EPI_RESID);
-      else if (pro == PRO_NORM && epi == EPI_SWIGLU) RT_MT(PRO_NORM, EPI_SWIGLU);
-      else if (pro == PRO_PLAIN && epi == EPI_SWIGLU) RT_MT(PRO_PLAIN, EPI_SWIGLU);
-      else if (pro == PRO_NORM && epi == EPI_ROPE) RT_MT(PRO_NORM, EPI_ROPE);
-      else if (pro == PRO_PLAIN && epi == EPI_ROPE) RT_MT(PRO_PLAIN, EPI_ROPE);
-      else return -2;
-#undef RT_MT
-      return hipGetLastError() == hipSuccess ? 0 : -6;
-    }
-  }
-  // CU-balanced variant (split_mode bit 0): whole plain/norm tiles + split remainder (not for
-  // NORM_ADD, whose workgroup 0 publishes the whole K row). ROPE finishes its pairs after the
-  // hand-off (partner = adjacent lane's combined sum); the decode path does not use it for qkv:
-  // Llama-3-8B qkv (384 tiles) measured 11.02 us plain vs 12.28 us balanced
-  // (profiles/experiments/README_r02.md)
-  if (split_ws != nullptr && (split_mode & 1) && pro != PRO_NORM_ADD && (K / 32) % 2 == 0 && K >= 64) {
-    const int cus = device_cus();
-    const int T = N / 16;
-    const int R = cus > 0 ? T % cus : 0;
-    if (cus > 0 && T > cus && R > 0 && R <= SPLIT_CTRS && split_ws_ints >= split_workspace_ints(R)) {
-      GemmArgs args{(uint16_t*)out, (const uint16_t*)x, (const short8*)Ws, (uint16_t*)res, M, N, K, ldo,
-                    eps, re, nullptr, nullptr};
-      args.kmajor = forced_order();
-      const dim3 grid(T + R);
-      // the two halves of a remainder tile on one XCD (RT_BAL_XCD=0: adjacent block ids, r02)
-      static const int bal_xpair = !(getenv("RT_BAL_XCD") && getenv("RT_BAL_XCD")[0] == '0');
-      if (pro == PRO_NORM && epi == EPI_ROPE)
-        hipLaunchKernelGGL((skinny_gemm_bal_kernel<PRO_NORM, EPI_ROPE, 4, 2>), grid, dim3(256), 0, stream, args,
-                           split_ws, R, bal_xpair);
-      else if (pro == PRO_PLAIN && epi == EPI_ROPE)
-        hipLaunchKernelGGL((skinny_gemm_bal_kernel<PRO_PLAIN, EPI_ROPE, 4, 2>), grid, dim3(256), 0, stream, args,
-                           split_ws, R, bal_xpair);
-      else if (pro == PRO_NORM && epi == EPI_SWIGLU)
-        hipLaunchKernelGGL((skinny_gemm_bal_kernel<PRO_NORM, EPI_SWIGLU, 4, 2>), grid, dim3(256), 0, stream, args,
-                           split_ws, R, bal_xpair);
-      else if (pro == PRO_PLAIN && epi == EPI_SWIGLU)
-        hipLaunchKernelGGL((skinny_gemm_bal_kernel<PRO_PLAIN, EPI_SWIGLU, 4, 2>), grid, dim3(256), 0, stream, args,
-                           split_ws, R, bal_xpair);
-      else if (pro == PRO_NORM && epi == EPI_STORE)
-        hipLaunchKernelGGL((skinny_gemm_bal_kernel<PRO_NORM, EPI_STORE, 4, 2>), grid, dim3(256), 0, stream, args,
-                           split_ws, R, bal_xpair);
-      else if (pro == PRO_PLAIN && epi == EPI_STORE)
-        hipLaunchKernelGGL((skinny_gemm_bal_kernel<PRO_PLAIN, EPI_STORE, 4, 2>), grid, dim3(256), 0, stream, args,
-                           split_ws, R, bal_xpair);
-      else if (pro == PRO_PLAIN && epi == EPI_RESID)
-        hipLaunchKernelGGL((skinny_gemm_bal_kernel<PRO_PLAIN, EPI_RESID, 4, 2>), grid, dim3(256), 0, stream, args,
-                           split_ws, R, bal_xpair);
-      else
-        return -2;
-      return 0;
-    }
-  }
-  // Variant = (waves per workgroup NW, k-steps per stage U). Since the pipeline's waits are
-  // counted (skinny_core.h gemm_tile), 4 waves win on every decode shape: U = 2 for the wide
-  // GEMMs (>= 384 column tiles: qkv 11.5, gate_up 39.0 us), U = 4 for the 256-tile o / down
-  // (8.05 / 20.9 us; U = 2 loses there) — profiles/r01_microbench_v3_cfg_sweep.log, v4, v5
-  // (4x1, 2x2, 2x4 lose on every shape).
-  // Before the counted waits the narrow projections needed 8 waves to keep bytes in flight.
-  // RT_SKINNY_CFG=<NW>x<U> (4x2, 8x2, 4x4, 8x4, 8x8, 4x8) pins one for microbenchmarks.
-  static const int cfg_env = [] {
-    const char* e = getenv("RT_SKINNY_CFG");
-    if (!e) return 0;
-    int nw = 0, u = 0;
-    if (sscanf(e, "%dx%d", &nw, &u) != 2) return 0;
-    return nw * 100 + u;
-  }();
-  // 129-224 tiles of >= 64 KB (tensor-parallel shards: tp2 qkv 192 tiles) stream on most of the
-  // CUs: 8 waves keep twice the bytes in flight per CU (tp2 qkv norm+rope 7.86 -> 7.34 us;
-  // tools/probes/stream_probe.hip 192 x 128 KB 8x2 6.53 / 4x4 6.99 us). Fewer tiles (48-96) stay
-  // at 4 x 4: 16 x 2 streams faster there in the probe (48 x 128 KB 5.32 vs 6.00 us) but loses in
-  // the GEMM (tp8 qkv 6.74 -> 7.24 us: the 16-wave LDS reduction and epilogue).
-  const int T16 = N / 16;
-  int cfg_shape = T16 >= 384 ? 402 : 404;
-  if (K >= 2048 && T16 > 128 && T16 <= 224) cfg_shape = 802;
-  const int cfg = cfg_env ? cfg_env : cfg_shape;
-  dim3 grid(N / 16);
-  const bool alds = !cfg_env && use_alds(M, K, N / 16, device_cus());
-  const size_t lds = alds ? (size_t)skinny::alds_bytes(M, K) : 0;
-#define RT_SG(P, E)                                                                                          \
-  do {                                                                                                       \
-    switch (cfg) {                                                                                           \
-      case 402: RT_SGV(P, E, 4, 2); break;                                                                   \
-      case 1602: RT_SGV(P, E, 16, 2); break;                                                                 \
-      case 802: RT_SGV(P, E, 8, 2); break;                                                                   \
-      case 408: RT_SGV(P, E, 4, 8); break;                                                                   \
-      case 804: RT_SGV(P, E, 8, 4); break;                                                                   \
-      case 808: RT_SGV(P, E, 8, 8); break;                                                                   \
-      default: RT_SGV(P, E, 4, 4); break;                                                                    \
-    }                                                                                                        \
-  } while (0)
+  const SkinnyPlan pl =
+      plan_skinny_gemm(wt, M, N, K, pro, epi, device_cus(), split_ws != nullptr, split_ws_ints, split_mode, knobs());
+  if (pl.rc != 0) return pl.rc;
   GemmArgs args{(uint16_t*)out, (const uint16_t*)x, (const short8*)Ws, (uint16_t*)res, M, N, K, ldo,
                 eps, re, (const uint16_t*)x2, (uint16_t*)xo};
-  args.kmajor = forced_order();
-#define RT_SGV(P, E, NWV, UV)                                                                                  \
-  do {                                                                                                         \
-    if (alds)                                                                                                  \
-      hipLaunchKernelGGL((skinny_gemm_alds_kernel<P, E, NWV, UV>), grid, dim3(NWV * 64), lds, stream, args);   \
-    else                                                                                                       \
-      hipLaunchKernelGGL((skinny_gemm_kernel<P, E, NWV, UV>), grid, dim3(NWV * 64), 0, stream, args);          \
-  } while (0)
-  if (pro == PRO_PLAIN && epi == EPI_STORE) RT_SG(PRO_PLAIN, EPI_STORE);
-  else if (pro == PRO_NORM && epi == EPI_STORE) RT_SG(PRO_NORM, EPI_STORE);
-  else if (pro == PRO_PLAIN && epi == EPI_RESID) RT_SG(PRO_PLAIN, EPI_RESID);
-  else if (pro == PRO_NORM && epi == EPI_SWIGLU) RT_SG(PRO_NORM, EPI_SWIGLU);
-  else if (pro == PRO_PLAIN && epi == EPI_SWIGLU) RT_SG(PRO_PLAIN, EPI_SWIGLU);
-  else if (pro == PRO_NORM && epi == EPI_ROPE) RT_SG(PRO_NORM, EPI_ROPE);
-  else if (pro == PRO_PLAIN && epi == EPI_ROPE) RT_SG(PRO_PLAIN, EPI_ROPE);
-  else if (pro == PRO_NORM_ADD && epi == EPI_STORE) RT_SG(PRO_NORM_ADD, EPI_STORE);
-  else if (pro == PRO_NORM_ADD && epi == EPI_SWIGLU) RT_SG(PRO_NORM_ADD, EPI_SWIGLU);
-  else if (pro == PRO_NORM_ADD && epi == EPI_ROPE) RT_SG(PRO_NORM_ADD, EPI_ROPE);
-  else return -2;
-#undef RT_SG
-#undef RT_SGV
-  return 0;
+  args.kmajor = resolve_order(N / 16, K, epi == EPI_SWIGLU, epi == EPI_ROPE);
+  args.wscale = wscale;
+  return f8 ? launch_plan<WT_FP8>(pl, args, pro, epi, split_ws, stream)
+            : launch_plan<WT_BF16>(pl, args, pro, epi, split_ws, stream);
 }
 
-int launch_shuffle_weight(void* Ws, const void* W, const void* gamma, int N, int K, int rope_rows, int D, int swiglu,
-                          hipStream_t stream) {
-  if (K % 32 || N % 16 || rope_rows > N || (rope_rows > 0 && (D <= 0 || D % 2 || rope_rows % D))) return -1;
-  if (swiglu && (N % 32 || rope_rows > 0)) return -1;
-  const int64_t total = (int64_t)N * K / 8;
-  int64_t grid = (total + 255) / 256;
-  if (grid > 8192) grid = 8192;
-  hipLaunchKernelGGL(shuffle_kernel, dim3((unsigned)grid), dim3(256), 0, stream, (short8*)Ws, (const uint16_t*)W,
-                     (const uint16_t*)gamma, N, K, rope_rows, D, swiglu, forced_order());
-  return 0;
+// Ws[rec] = W[src][k0 .. k0+8) (optionally W * gamma[k] folded in), skinny_core.h lane_record
+__global__ void shuffle_kernel(short8* __restrict__ Ws, const uint16_t* __restrict__ W,
+                               const uint16_t* __restrict__ gamma, int N, int K, int rope_rows, int D, int swiglu,
+                               int order) {
+  const int64_t total = lane_records<WT_BF16>(N, K);
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const LaneRec r = lane_record<WT_BF16>(i, N, K, rope_rows, D, swiglu != 0, order);
+    short8 v = *reinterpret_cast<const short8*>(W + (size_t)r.src * K + r.k0);
+    if (gamma != nullptr) {
+      const short8 gv = *reinterpret_cast<const short8*>(gamma + r.k0);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = (short)rt::f2bf(rt::bf2f((uint16_t)v[j]) * rt::bf2f((uint16_t)gv[j]));
+    }
+    Ws[r.rec] = v;
+  }
+}
+
+// Exact inverse of shuffle_kernel's permutation (gamma, if any, stays folded): the row-major
+// weight for the prefill GEMMs when only the shuffled copy is kept resident (70B on one GPU).
+__global__ void unshuffle_kernel(uint16_t* __restrict__ W, const short8* __restrict__ Ws, int N, int K, int rope_rows,
+                                 int D, int swiglu, int order) {
+  const int64_t total = lane_records<WT_BF16>(N, K);
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const LaneRec r = lane_record<WT_BF16>(i, N, K, rope_rows, D, swiglu != 0, order);
+    *reinterpret_cast<short8*>(W + (size_t)r.src * K + r.k0) = Ws[r.rec];
+  }
+}
+}  // namespace
+
+int split_workspace_ints(int max_split_tiles) { return split_words(max_split_tiles); }
+int splitk_parts(int T, int ks, int cus, int64_t ws_ints) { return skinny::splitk_parts(T, ks, cus, ws_ints, knobs()); }
+
+int launch_skinny_gemm(void* out, const void* x, const void* Ws, void* res, int M, int N, int K, int ldo, float eps,
+                       int pro, int epi, const void* rope, const void* x2, void* xo, hipStream_t stream,
+                       int* split_ws, int64_t split_ws_ints, int split_mode) {
+  return launch_gemm(WT_BF16, out, x, Ws, nullptr, res, M, N, K, ldo, eps, pro, epi, rope, x2, xo, stream, split_ws,
+                     split_ws_ints, split_mode);
 }
 
 int launch_skinny_gemm_rope(void* q_out, const void* x, const void* Ws, int M, int K, int pro, float eps,
@@ -587,6 +312,40 @@ int launch_skinny_gemm_rope(void* q_out, const void* x, const void* Ws, int M, i
                             hipStream_t stream, int* split_ws, int64_t split_ws_ints, int split_mode,
                             const float* bias) {
   const RopeEpi re{positions, cos_sin, (uint16_t*)k_cache, (uint16_t*)v_cache, slots, Hq, Hkv, D, BS, bias};
-  return launch_skinny_gemm(q_out, x, Ws, nullptr, M, (Hq + 2 * Hkv) * D, K, 0, eps, pro, EPI_ROPE, &re, x2, xo,
-                            stream, split_ws, split_ws_ints, split_mode);
+  return launch_gemm(WT_BF16, q_out, x, Ws, nullptr, nullptr, M, (Hq + 2 * Hkv) * D, K, 0, eps, pro, EPI_ROPE, &re, x2,
+                     xo, stream, split_ws, split_ws_ints, split_mode);
+}
+
+// fp8 weights (Wq, scale: gemm_skinny_fp8.hip): always one tile per workgroup, no workspace
+int launch_skinny_gemm_fp8(void* out, const void* x, const void* Wq, const float* scale, void* res, int M, int N,
+                           int K, int ldo, float eps, int pro, int epi, const void* rope, hipStream_t stream) {
+  return launch_gemm(WT_FP8, out, x, Wq, scale, res, M, N, K, ldo, eps, pro, epi, rope, nullptr, nullptr, stream,
+                     nullptr, 0, 0);
+}
+
+int launch_skinny_gemm_rope_fp8(void* q_out, const void* x, const void* Wq, const float* scale, int M, int K, int pro,
+                                float eps, const int64_t* positions, const float* cos_sin, void* k_cache,
+                                void* v_cache, const int64_t* slots, int Hq, int Hkv, int D, int BS,
+                                const float* bias, hipStream_t stream) {
+  const RopeEpi re{positions, cos_sin, (uint16_t*)k_cache, (uint16_t*)v_cache, slots, Hq, Hkv, D, BS, bias};
+  return launch_skinny_gemm_fp8(q_out, x, Wq, scale, nullptr, M, (Hq + 2 * Hkv) * D, K, 0, eps, pro, EPI_ROPE, &re,
+                                stream);
+}
+
+int launch_shuffle_weight(void* Ws, const void* W, const void* gamma, int N, int K, int rope_rows, int D, int swiglu,
+                          hipStream_t stream) {
+  if (!weight_shape_ok<WT_BF16>(N, K, rope_rows, D, swiglu)) return -1;
+  hipLaunchKernelGGL(shuffle_kernel, shuffle_grid(lane_records<WT_BF16>(N, K), 8192), dim3(256), 0, stream,
+                     (short8*)Ws, (const uint16_t*)W, (const uint16_t*)gamma, N, K, rope_rows, D, swiglu,
+                     shuffle_order(N, K, rope_rows, swiglu));
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_unshuffle_weight(void* W, const void* Ws, int N, int K, int rope_rows, int D, int swiglu,
+                            hipStream_t stream) {
+  if (!weight_shape_ok<WT_BF16>(N, K, rope_rows, D, swiglu)) return -1;
+  hipLaunchKernelGGL(unshuffle_kernel, shuffle_grid(lane_records<WT_BF16>(N, K), 65536), dim3(256), 0, stream,
+                     (uint16_t*)W, (const short8*)Ws, N, K, rope_rows, D, swiglu,
+                     shuffle_order(N, K, rope_rows, swiglu));
+  return hipGetLastError() == hipSuccess ? 0 : -2;
 }

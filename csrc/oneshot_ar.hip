@@ -30,7 +30,7 @@
 // has no separate all-reduce launch at all, and a tile's xGMI round trip overlaps the other
 // tiles' weight streams. Both forms share the receive buffers and the call counter (a call of
 // either kind is one epoch), so they interleave freely within a captured graph.
-#include "skinny_core.h"
+#include "skinny_plan.h"
 
 #include <cstdio>
 #include <cstring>
@@ -444,6 +444,7 @@ int oneshot_gemm_ar(int id, void* out, const void* x, const void* Ws, int M, int
     if (c->peers.data[p] == nullptr || c->peer_tflags[p] == nullptr) return -3;
   skinny::GemmArgs args{(uint16_t*)out, (const uint16_t*)x, (const rt::short8*)Ws, (uint16_t*)res, M, N, K, N, 0.f,
                         skinny::RopeEpi{}, nullptr, nullptr};
+  args.kmajor = skinny::resolve_order(N / 16, K, false, false);   // as shuffle_weight wrote it, RT_WEIGHT_ORDER included
   for (int p = 0; p < c->world; ++p) {
     args.ar.data[p] = c->peers.data[p];
     args.ar.tflags[p] = c->peer_tflags[p];

@@ -1,5 +1,5 @@
 // Device core of the decode-path GEMMs (M <= 16 rows; 17..32 through gemm_tiles): shared by the standalone launches in
-// gemm_skinny.hip and the persistent decode-layer kernel in decode_layer.hip.
+// gemm_skinny.hip (whose launch plan is skinny_plan.h) and the persistent decode-layer kernel in decode_layer.hip.
 //
 // Weight layout ("fragment-shuffled", built once at load time by `shuffle_weight`):
 //     Ws[N/16][K/32][64 lanes][8]   with  Ws[t][s][l][j] = W[16t + (l&15)][32s + 8(l>>4) + j]
@@ -25,7 +25,7 @@
 // SC1 = true (persistent kernel): activations produced inside the same launch are read with
 // sc1 loads and every output is stored sc1 (write-through), MI355X_MICROARCH "Valid forms".
 //
-// FP8 weights (WT = WT_FP8, built by `shuffle_weight_fp8`, launched from gemm_skinny_fp8.hip):
+// FP8 weights (WT = WT_FP8, built by `shuffle_weight_fp8` in gemm_skinny_fp8.hip, launched from gemm_skinny.hip):
 // OCP e4m3fn codes with one fp32 scale per weight row (W8A16: activations stay bf16). One record
 // is still 64 lanes x 16 B = 1 KiB, but 64 deep in k — a lane holds 16 CONSECUTIVE k of its row:
 //     Wq[N/16][K/64][64 lanes][16]  with  Wq[t][s][l][j] = code(W[16t + (l&15)][64s + 16(l>>4) + j])
@@ -173,45 +173,90 @@ struct Stage {
 template <int EPI>
 constexpr size_t krec() { return (EPI == EPI_SWIGLU) ? 128 : 64; }
 
-// Weight record order, chosen from the shape so that the shuffle (gemm_skinny.hip) and every
-// GEMM launch agree without carrying a layout tag: 0 = tile-major (one contiguous panel per
+// Weight record order, chosen from the shape (or pinned: skinny_plan.h resolve_order, which the
+// shuffles and every GEMM launch go through, so they agree without carrying a layout tag): 0 = tile-major (one contiguous panel per
 // tile); c > 0 = k-chunks of 2^(c-1) steps (all tiles' chunks for one k range adjacent, so the
 // concurrently streaming workgroups spread over every HBM channel instead of camping on a few
 // long panels). tools/exp_balance.hip layouts, MI355X, M = 3: down (K 14336, 1 tile per CU)
 // 20.97 -> 19.70 us k-major; qkv 11.25 -> 10.82 chunks of 4; gate_up 39.2-39.9 -> 38.7-39.0
 // chunks of 16; lm_head 157.3 -> 148.3 chunks of 16; o (K 4096) unchanged, kept tile-major.
-__host__ __device__ inline int weight_order(int tiles, int ksteps, bool swiglu, bool rope) {
+// An order is a property of the shape, not of the weight type: chunks are counted in 32-deep
+// bf16 k-steps of K, and an fp8 weight of the same shape takes the same order (chunk_log2).
+// chunks of 2^(order-1) 32-deep k-steps must tile K exactly (order 0 always does)
+__host__ __device__ inline bool order_tiles(int order, int K) {
+  return order == 0 || (order > 0 && order <= 24 && (K / 32) % (1 << (order - 1)) == 0);
+}
+__host__ __device__ inline int weight_order(int tiles, int K, bool swiglu, bool rope) {
   int order = 0;
   if (swiglu) order = 5;
   else if (rope) order = 3;
   else if (tiles >= 4096) order = 5;
-  else if (ksteps >= 384) order = 1;
-  if (order > 0 && ksteps % (1 << (order - 1)) != 0) order = 0;   // chunks must tile K exactly
+  else if (K / 32 >= 384) order = 1;
+  if (order > 0 && (K / 32) % (1 << (order - 1)) != 0) order = 0;   // chunks must tile K exactly
   return order;
 }
 
-// index of the first record of (tile t, k-step s) in a layout of T tiles x ks steps
-__host__ __device__ inline size_t rec_index(int t, int s, int T, int ks, int order, int recs) {
-  if (order <= 0) return ((size_t)t * ks + s) * recs;
-  const int lc = order - 1, C = 1 << lc;
-  return ((size_t)(s >> lc) * T * C + (size_t)t * C + (s & (C - 1))) * recs;
-}
-
-// FP8: the record order of the bf16 weight of the same shape (K / 32 bf16 k-steps), the chunks
-// covering the same k range, i.e. half as many 64-deep records (k-major stays one record)
-__host__ __device__ inline int weight_order_fp8(int tiles, int K, bool swiglu, bool rope) {
-  return weight_order(tiles, K / 32, swiglu, rope);
-}
-// log2(records per chunk) of `order` > 0 for weight type WT
+// log2(records per chunk) of `order` > 0 for weight type WT. FP8: the chunks cover the same k
+// range as the bf16 weight's, i.e. half as many 64-deep records (k-major stays one record)
 template <int WT>
 __host__ __device__ inline int chunk_log2(int order) {
   return WT == WT_FP8 ? (order >= 2 ? order - 2 : 0) : order - 1;
 }
-// rec_index for 64-deep fp8 records (s, ks in records)
-__host__ __device__ inline size_t rec_index_fp8(int t, int s, int T, int ks, int order, int recs) {
+// index of the first record of (tile t, k-step s) in a layout of T tiles x ks steps (s, ks in
+// records of kdeep<WT>() k elements)
+template <int WT>
+__host__ __device__ inline size_t rec_index(int t, int s, int T, int ks, int order, int recs) {
   if (order <= 0) return ((size_t)t * ks + s) * recs;
-  const int lc = chunk_log2<WT_FP8>(order), C = 1 << lc;
+  const int lc = chunk_log2<WT>(order), C = 1 << lc;
   return ((size_t)(s >> lc) * T * C + (size_t)t * C + (s & (C - 1))) * recs;
+}
+
+// source row of output (epilogue-order) row `row`: output row r = h*D + p < rope_rows takes
+// source row h*D + (p>>1) + (p&1)*D/2, the pair-interleaved q/k order the ROPE epilogue expects
+__host__ __device__ inline int source_row(int row, int rope_rows, int D) {
+  if (row < rope_rows) {
+    const int h = row / D, p = row - h * D;
+    row = h * D + (p >> 1) + (p & 1) * (D >> 1);
+  }
+  return row;
+}
+
+// The weight-layout map: lane record i of [0, N/16 * K/kdeep * 64) — the 16 bytes one lane of
+// one wave load holds — is
+//     Ws[t][s][l][..] = W[16t + (l&15)][kdeep*s + (kdeep/4)(l>>4) ..]
+// (SwiGLU, N = 2I rows [gate; up], k-step-paired: Ws[t][s][h][l][..] = W[h*I + 16t + (l&15)][..]).
+// The shuffle / quantise kernels write W[src][k0..] to Ws[rec], the unshuffle / dequantise
+// kernels read it back, and the GEMMs (tile_base) walk the same order.
+struct LaneRec {
+  int orow;    // row in the epilogue's order (indexes the fp8 scales)
+  int src;     // row of the row-major weight (ROPE rows pair-interleaved)
+  int k0;      // first k of the record's kdeep/4 consecutive elements
+  size_t rec;  // offset in 16-byte records
+};
+template <int WT>
+__host__ __device__ inline int64_t lane_records(int N, int K) {
+  return (int64_t)(N / 16) * (K / kdeep<WT>()) * 64;
+}
+template <int WT>
+__host__ __device__ inline LaneRec lane_record(int64_t i, int N, int K, int rope_rows, int D, bool swiglu,
+                                               int order) {
+  const int nsteps = K / kdeep<WT>();
+  const int T = swiglu ? N / 32 : N / 16;   // output tiles (SwiGLU: gate + up rows per tile)
+  const int l = (int)(i & 63);
+  int64_t ts = i >> 6;
+  int h = 0;
+  if (swiglu) {
+    h = (int)(ts & 1);
+    ts >>= 1;
+  }
+  const int s = (int)(ts % nsteps);
+  const int t = (int)(ts / nsteps);
+  LaneRec r;
+  r.orow = 16 * t + (l & 15) + h * (N / 2);
+  r.src = source_row(r.orow, rope_rows, D);
+  r.k0 = kdeep<WT>() * s + (kdeep<WT>() / 4) * (l >> 4);
+  r.rec = rec_index<WT>(t, s, T, nsteps, order, swiglu ? 128 : 64) + h * 64 + l;
+  return r;
 }
 
 struct WStride {
@@ -243,7 +288,7 @@ template <int EPI, int WT = WT_BF16>
 RT_DEVICE const short8* tile_base(const GemmArgs& p, int tile, WStride& ws) {
   const size_t T = (size_t)p.N / 16, ks = (size_t)p.K / kdeep<WT>();
   const int order = p.kmajor >= 0 ? p.kmajor
-                                  : weight_order((int)T, p.K / 32, EPI == EPI_SWIGLU, EPI == EPI_ROPE);
+                                  : weight_order((int)T, p.K, EPI == EPI_SWIGLU, EPI == EPI_ROPE);
   if (order <= 0) {
     ws.lc = 30;
     ws.cstride = 0;

@@ -6,6 +6,9 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <vector>
+
+#include "skinny_plan.h"
 
 int launch_skinny_gemm(void* out, const void* x, const void* Ws, void* res, int M, int N, int K, int ldo, float eps,
                        int pro, int epi, const void* rope, const void* x2, void* xo, hipStream_t stream,
@@ -29,6 +32,12 @@ int launch_kv_block_copy(void* k, void* v, const int* src, const int* dst, int n
                          int64_t block_elems, hipStream_t stream);
 int launch_unshuffle_weight(void* W, const void* Ws, int N, int K, int rope_rows, int D, int swiglu,
                             hipStream_t stream);
+int launch_skinny_gemm_fp8(void* out, const void* x, const void* Wq, const float* scale, void* res, int M, int N,
+                           int K, int ldo, float eps, int pro, int epi, const void* rope, hipStream_t stream);
+int launch_shuffle_weight_fp8(void* Wq, float* scale, float* amax, const void* W, const void* gamma, int N, int K,
+                              int rope_rows, int D, int swiglu, hipStream_t stream);
+int launch_unshuffle_weight_fp8(void* W, const void* Wq, const float* scale, int N, int K, int rope_rows, int D,
+                                int swiglu, hipStream_t stream);
 
 static int failures = 0;
 #define EXPECT(cond)                                                   \
@@ -38,6 +47,127 @@ static int failures = 0;
       ++failures;                                                      \
     }                                                                  \
   } while (0)
+
+// The lane-record map (skinny_core.h) on an [N, K] weight: every lane record mapped forward; the
+// record offsets must be a permutation of [0, N*K / record) and (source row, k0) must cover the
+// matrix exactly once.
+template <int WT>
+static void check_layout(int N, int K, int rope_rows, int D, bool swiglu, int order) {
+  constexpr int kelem = skinny::kdeep<WT>() / 4;   // k elements of one lane record (16 bytes)
+  const int64_t total = skinny::lane_records<WT>(N, K);
+  EXPECT(total == (int64_t)N * K / kelem);
+  std::vector<int> rec_seen(total, 0), src_seen(total, 0);
+  for (int64_t i = 0; i < total; ++i) {
+    const skinny::LaneRec r = skinny::lane_record<WT>(i, N, K, rope_rows, D, swiglu, order);
+    const bool in_range = r.rec < (size_t)total && r.orow >= 0 && r.orow < N && r.src >= 0 && r.src < N &&
+                          r.k0 >= 0 && r.k0 % kelem == 0 && r.k0 + kelem <= K;
+    EXPECT(in_range);
+    if (!in_range) return;
+    ++rec_seen[r.rec];
+    ++src_seen[(int64_t)r.src * (K / kelem) + r.k0 / kelem];
+    // rows outside the ROPE block keep their place; inside it they stay within their head
+    EXPECT(r.orow >= rope_rows ? r.src == r.orow : r.src / D == r.orow / D);
+  }
+  for (int64_t i = 0; i < total; ++i) EXPECT(rec_seen[i] == 1 && src_seen[i] == 1);
+}
+
+// plan of a bf16 / fp8 decode GEMM on 256 CUs with the workspace of 1024 split tiles, default knobs
+static skinny::SkinnyPlan plan(int wt, int M, int N, int K, int pro, int epi, int split_mode, bool ws = true,
+                               const skinny::SkinnyKnobs& kn = skinny::SkinnyKnobs{}) {
+  return skinny::plan_skinny_gemm(wt, M, N, K, pro, epi, 256, ws, ws ? 256 + 1024 * 528 : 0, split_mode, kn);
+}
+static bool is(const skinny::SkinnyPlan& p, int form, int NW, int U, int grid, int TN = 1, int MB = 1, int S = 1,
+               int R = 0) {
+  return p.rc == 0 && p.form == form && p.NW == NW && p.U == U && p.block == NW * 64 && p.grid == grid &&
+         p.TN == TN && p.MB == MB && p.S == S && p.R == R && p.lds_bytes == 0 && !p.alds;
+}
+
+static void check_plans() {
+  using namespace skinny;
+  const int BF = WT_BF16, F8 = WT_FP8;
+  // decode (M = 3), Llama-3-8B shapes
+  EXPECT(is(plan(BF, 3, 6144, 4096, PRO_NORM, EPI_ROPE, 2), ONE_TILE, 4, 2, 384));
+  EXPECT(is(plan(BF, 3, 4096, 4096, PRO_PLAIN, EPI_RESID, 2), ONE_TILE, 4, 4, 256));
+  EXPECT(is(plan(BF, 3, 14336, 4096, PRO_NORM, EPI_SWIGLU, 3), BALANCED, 4, 2, 1024, 1, 1, 1, 128));
+  EXPECT(is(plan(BF, 3, 14336, 4096, PRO_NORM, EPI_SWIGLU, 2), ONE_TILE, 4, 2, 896));
+  EXPECT(is(plan(BF, 3, 4096, 14336, PRO_PLAIN, EPI_RESID, 3), ONE_TILE, 4, 4, 256));
+  EXPECT(is(plan(BF, 3, 128256, 4096, PRO_NORM, EPI_STORE, 2), ONE_TILE, 4, 2, 8016));
+  // tensor-parallel shards
+  EXPECT(is(plan(BF, 3, 3072, 4096, PRO_NORM, EPI_ROPE, 2), ONE_TILE, 8, 2, 192));
+  EXPECT(is(plan(BF, 3, 768, 4096, PRO_NORM, EPI_ROPE, 2), SPLITK, 8, 2, 240, 1, 1, 5));
+  EXPECT(is(plan(BF, 3, 768, 4096, PRO_NORM, EPI_ROPE, 0), ONE_TILE, 4, 4, 48));
+  EXPECT(is(plan(BF, 3, 1792, 4096, PRO_NORM, EPI_SWIGLU, 2), SPLITK, 8, 2, 224, 1, 1, 2));
+  // serving batches
+  EXPECT(is(plan(BF, 8, 4096, 4096, PRO_PLAIN, EPI_RESID, 2), ONE_TILE, 4, 4, 256));
+  EXPECT(is(plan(BF, 16, 6144, 4096, PRO_NORM, EPI_ROPE, 2), MULTI, 4, 2, 192, 2, 1));
+  EXPECT(is(plan(BF, 16, 14336, 4096, PRO_NORM, EPI_SWIGLU, 3), MULTI, 4, 2, 224, 4, 1));
+  EXPECT(is(plan(BF, 16, 4096, 4096, PRO_PLAIN, EPI_RESID, 2), MULTI_SPLIT, 4, 2, 256, 2, 1, 2));
+  EXPECT(is(plan(BF, 16, 4096, 4096, PRO_PLAIN, EPI_RESID, 2, false), ONE_TILE, 4, 4, 256));
+  EXPECT(is(plan(BF, 20, 6144, 4096, PRO_NORM, EPI_ROPE, 2), MULTI, 4, 2, 192, 2, 2));
+  EXPECT(is(plan(BF, 20, 14336, 4096, PRO_NORM, EPI_SWIGLU, 3), MULTI, 4, 2, 448, 2, 2));
+  EXPECT(is(plan(BF, 20, 4096, 4096, PRO_PLAIN, EPI_RESID, 2), MULTI_SPLIT, 4, 2, 256, 2, 2, 2));   // workspace exactly large enough
+  // the allowed (pro, epi) sets: bf16 (NORM, RESID) only in the serving-batch forms; NORM_ADD never balanced / multi
+  EXPECT(plan(BF, 3, 4096, 4096, PRO_NORM, EPI_RESID, 3).rc == -2);
+  EXPECT(plan(BF, 3, 768, 4096, PRO_NORM, EPI_RESID, 3).rc == -2);
+  EXPECT(plan(BF, 5, 4096, 4096, PRO_NORM, EPI_RESID, 3).rc == -2);   // 5 rows, but still one tile
+  EXPECT(plan(BF, 16, 4096, 4096, PRO_NORM, EPI_RESID, 3).form == MULTI_SPLIT);
+  EXPECT(is(plan(BF, 16, 14336, 4096, PRO_NORM_ADD, EPI_SWIGLU, 3), ONE_TILE, 4, 2, 896));
+  EXPECT(plan(BF, 3, 4096, 4096, PRO_NORM_ADD, EPI_RESID, 3).rc == -2);
+  EXPECT(plan(BF, 3, 4096, 4096, PRO_PLAIN, EPI_AR, 3).rc == -2);
+  // fp8: always one tile, no knob, every PLAIN / NORM pair
+  EXPECT(is(plan(F8, 3, 6144, 4096, PRO_NORM, EPI_ROPE, 3), ONE_TILE, 4, 2, 384));
+  EXPECT(is(plan(F8, 3, 4096, 14336, PRO_NORM, EPI_RESID, 3), ONE_TILE, 4, 4, 256));
+  EXPECT(is(plan(F8, 16, 768, 4096, PRO_PLAIN, EPI_SWIGLU, 3), ONE_TILE, 4, 4, 48));
+  EXPECT(plan(F8, 3, 4096, 4096, PRO_NORM_ADD, EPI_STORE, 3).rc == -2);
+  // every knob still steers the plan
+  SkinnyKnobs k;
+  k.splitk = 1;
+  EXPECT(is(plan(BF, 3, 768, 4096, PRO_NORM, EPI_ROPE, 2, true, k), ONE_TILE, 4, 4, 48));
+  k = SkinnyKnobs{}, k.splitk = 3;
+  EXPECT(is(plan(BF, 3, 768, 4096, PRO_NORM, EPI_ROPE, 2, true, k), SPLITK, 8, 2, 144, 1, 1, 3));
+  k = SkinnyKnobs{}, k.splitk_target = 512;
+  EXPECT(is(plan(BF, 3, 768, 4096, PRO_NORM, EPI_ROPE, 2, true, k), SPLITK, 8, 2, 48 * 11, 1, 1, 11));
+  k = SkinnyKnobs{}, k.splitk_cfg = 404;
+  EXPECT(is(plan(BF, 3, 768, 4096, PRO_NORM, EPI_ROPE, 2, true, k), SPLITK, 4, 4, 240, 1, 1, 5));
+  k = SkinnyKnobs{}, k.tn = 1;
+  EXPECT(is(plan(BF, 16, 6144, 4096, PRO_NORM, EPI_ROPE, 2, true, k), ONE_TILE, 4, 2, 384));
+  k = SkinnyKnobs{}, k.tn = 4;
+  EXPECT(is(plan(BF, 16, 6144, 4096, PRO_NORM, EPI_ROPE, 2, true, k), MULTI, 4, 2, 96, 4, 1));
+  k = SkinnyKnobs{}, k.tncfg = 802;
+  EXPECT(is(plan(BF, 16, 6144, 4096, PRO_NORM, EPI_ROPE, 2, true, k), MULTI, 8, 2, 192, 2, 1));
+  k = SkinnyKnobs{}, k.tncfg = 404;   // 4x4 exists for two tiles only
+  EXPECT(is(plan(BF, 16, 6144, 4096, PRO_NORM, EPI_ROPE, 2, true, k), MULTI, 4, 4, 192, 2, 1));
+  EXPECT(is(plan(BF, 16, 14336, 4096, PRO_NORM, EPI_SWIGLU, 2, true, k), MULTI, 4, 2, 224, 4, 1));
+  k = SkinnyKnobs{}, k.tn_minm = 3;
+  EXPECT(is(plan(BF, 3, 6144, 4096, PRO_NORM, EPI_ROPE, 2, true, k), MULTI, 4, 2, 192, 2, 1));
+  k = SkinnyKnobs{}, k.tns = 0;
+  EXPECT(is(plan(BF, 16, 4096, 4096, PRO_PLAIN, EPI_RESID, 2, true, k), ONE_TILE, 4, 4, 256));
+  k = SkinnyKnobs{}, k.tns = 2;
+  EXPECT(is(plan(BF, 8, 4096, 4096, PRO_PLAIN, EPI_RESID, 2, true, k), MULTI_SPLIT, 4, 2, 256, 2, 1, 2));
+  EXPECT(plan(BF, 3, 14336, 4096, PRO_NORM, EPI_SWIGLU, 3).xpair == 1);
+  k = SkinnyKnobs{}, k.bal_xcd = 0;
+  EXPECT(plan(BF, 3, 14336, 4096, PRO_NORM, EPI_SWIGLU, 3, true, k).xpair == 0);
+  k = SkinnyKnobs{}, k.cfg = 804;
+  EXPECT(is(plan(BF, 3, 6144, 4096, PRO_NORM, EPI_ROPE, 2, true, k), ONE_TILE, 8, 4, 384));
+  k = SkinnyKnobs{}, k.cfg = 303;   // not a compiled variant: 4x4
+  EXPECT(is(plan(BF, 3, 6144, 4096, PRO_NORM, EPI_ROPE, 2, true, k), ONE_TILE, 4, 4, 384));
+  k = SkinnyKnobs{}, k.alds = 1;   // staged rows: 64 + 3 * (4096 + 8) * 2 bytes of dynamic LDS
+  const SkinnyPlan a = plan(BF, 3, 4096, 4096, PRO_PLAIN, EPI_RESID, 2, true, k);
+  EXPECT(a.rc == 0 && a.form == ALDS && a.alds && a.NW == 4 && a.U == 4 && a.grid == 256 && a.lds_bytes == 24688);
+  const SkinnyPlan as = plan(BF, 3, 768, 4096, PRO_NORM, EPI_ROPE, 2, true, k);   // split-K parts of 26 (+1) k-steps
+  EXPECT(as.form == SPLITK && as.alds && as.S == 5 && as.block == 512 && as.lds_bytes == 64 + 3 * (32 * 27 + 8) * 2);
+  k = SkinnyKnobs{}, k.alds = 2;   // the shard rule: only with at most one workgroup per CU
+  EXPECT(plan(BF, 3, 3072, 4096, PRO_NORM, EPI_ROPE, 2, true, k).form == ALDS);
+  EXPECT(plan(BF, 3, 6144, 4096, PRO_NORM, EPI_ROPE, 2, true, k).form == ONE_TILE);
+  k.alds = 1;
+  EXPECT(plan(BF, 4, 4096, 14336, PRO_PLAIN, EPI_RESID, 0, true, k).form == ONE_TILE);   // 4 rows x 14336 do not fit
+  // RT_WEIGHT_ORDER: a pin holds where its chunks tile K, else tile-major; no pin = the shape rule
+  EXPECT(resolve_order(256, 14336, false, false, -1) == 1 && resolve_order(384, 4096, false, true, -1) == 3);
+  EXPECT(resolve_order(896, 4096, true, false, -1) == 5 && resolve_order(896, 256, true, false, -1) == 0);
+  EXPECT(resolve_order(256, 14336, false, false, 0) == 0 && resolve_order(256, 4096, false, false, 3) == 3);
+  EXPECT(resolve_order(4, 256, false, false, 4) == 4 && resolve_order(4, 256, false, false, 5) == 0);
+  EXPECT(resolve_order(4, 256, false, false, 99) == 0);
+}
 
 int main() {
   // decode GEMM: M outside [1, 32] (17..32 only with plain / norm prologues and no all-reduce), K not a
@@ -83,6 +213,34 @@ int main() {
   EXPECT(launch_kv_block_copy(nullptr, nullptr, nullptr, nullptr, 0, 32, 16, 8192, nullptr) == 0);
   EXPECT(launch_kv_block_copy(nullptr, nullptr, nullptr, nullptr, 2, 32, 16, 8190, nullptr) == -1);
   EXPECT(launch_kv_block_copy(nullptr, nullptr, nullptr, nullptr, 2, 0, 16, 8192, nullptr) == -1);
+  // fp8 launchers: M outside [1, 16], K not a multiple of 64, N not of 16, missing scale / ROPE
+  // operand, NORM_ADD; SwiGLU shuffles take no ROPE rows
+  const float* sc = (const float*)16;   // never dereferenced on the host
+  EXPECT(launch_skinny_gemm_fp8(nullptr, nullptr, nullptr, sc, nullptr, 0, 16, 64, 16, 1e-5f, 0, 0, nullptr, nullptr) == -1);
+  EXPECT(launch_skinny_gemm_fp8(nullptr, nullptr, nullptr, sc, nullptr, 17, 16, 64, 16, 1e-5f, 0, 0, nullptr, nullptr) == -1);
+  EXPECT(launch_skinny_gemm_fp8(nullptr, nullptr, nullptr, sc, nullptr, 3, 16, 96, 16, 1e-5f, 0, 0, nullptr, nullptr) == -1);
+  EXPECT(launch_skinny_gemm_fp8(nullptr, nullptr, nullptr, sc, nullptr, 3, 24, 64, 24, 1e-5f, 0, 0, nullptr, nullptr) == -1);
+  EXPECT(launch_skinny_gemm_fp8(nullptr, nullptr, nullptr, nullptr, nullptr, 3, 16, 64, 16, 1e-5f, 0, 0, nullptr, nullptr) == -1);
+  EXPECT(launch_skinny_gemm_fp8(nullptr, nullptr, nullptr, sc, nullptr, 3, 16, 64, 16, 1e-5f, 2, 0, nullptr, nullptr) == -2);
+  EXPECT(launch_skinny_gemm_fp8(nullptr, nullptr, nullptr, sc, nullptr, 3, 16, 64, 16, 1e-5f, 1, 3, nullptr, nullptr) == -3);
+  EXPECT(launch_shuffle_weight_fp8(nullptr, nullptr, nullptr, nullptr, nullptr, 64, 128, 32, 16, 1, nullptr) == -1);
+  EXPECT(launch_shuffle_weight_fp8(nullptr, nullptr, nullptr, nullptr, nullptr, 64, 96, 0, 0, 0, nullptr) == -1);
+  EXPECT(launch_unshuffle_weight_fp8(nullptr, nullptr, nullptr, 64, 128, 32, 16, 1, nullptr) == -1);
+  EXPECT(launch_unshuffle_weight_fp8(nullptr, nullptr, nullptr, 24, 128, 0, 0, 0, nullptr) == -1);
+  EXPECT(launch_shuffle_weight(nullptr, nullptr, nullptr, 64, 128, 32, 16, 1, nullptr) == -1);
+  EXPECT(launch_unshuffle_weight(nullptr, nullptr, 64, 128, 32, 16, 1, nullptr) == -1);
+  // the weight-layout map, N = 64, K = 256: tile-major and every chunked order that tiles K (8
+  // bf16 k-steps: chunks of 1, 2, 4, 8), with and without ROPE rows (2 heads of 16), SwiGLU
+  for (int order = 0; order <= 4; ++order) {
+    EXPECT(skinny::resolve_order(4, 256, false, false, order) == order);
+    for (int rope_rows = 0; rope_rows <= 32; rope_rows += 32) {
+      check_layout<skinny::WT_BF16>(64, 256, rope_rows, 16, false, order);
+      check_layout<skinny::WT_FP8>(64, 256, rope_rows, 16, false, order);
+    }
+    check_layout<skinny::WT_BF16>(64, 256, 0, 16, true, order);
+    check_layout<skinny::WT_FP8>(64, 256, 0, 16, true, order);
+  }
+  check_plans();
   // weight unshuffle: N%16, K%32, rope rows beyond N
   EXPECT(launch_unshuffle_weight(nullptr, nullptr, 24, 64, 0, 0, 0, nullptr) == -1);
   EXPECT(launch_unshuffle_weight(nullptr, nullptr, 32, 48, 0, 0, 0, nullptr) == -1);

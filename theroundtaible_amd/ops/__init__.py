@@ -388,7 +388,7 @@ def unshuffle_weight(Ws: torch.Tensor, rope_heads: int = 0, head_dim: int = 0, s
 
 # split-K / CU-balanced skinny GEMM workspace: 256 tile counters + 528 floats per tile part, up
 # to 1024 parts (split-K: T x S; balanced: 2 x (tile count mod CU count));
-# csrc/gemm_skinny.hip splitk_parts / split_workspace_ints
+# csrc/skinny_plan.h splitk_parts / split_words
 SPLIT_WS_INTS = 256 + 1024 * (16 * 16 * 2 + 16)
 SPLIT_K, SPLIT_BALANCE = 2, 1     # split_mode bits
 
