@@ -32,7 +32,7 @@ int launch_prefill(void* out, const void* q, const void* k_cache, const void* v_
                    int max_blocks, float scale, hipStream_t stream);
 int launch_sample(int64_t* out, const void* logits, bool is_bf16, int B, int V, int64_t ld_row,
                   const float* temperature, const float* top_p, const int* top_k, const int64_t* seeds,
-                  const int64_t* offsets, float* ws, hipStream_t stream, const void* advance);
+                  const int64_t* offsets, float* ws, hipStream_t stream);
 int launch_sample_advance(int64_t* tok, const void* logits, bool is_bf16, int B, int V, int64_t ld_row,
                           const float* temperature, const float* top_p, const int* top_k, const int64_t* seeds,
                           int64_t* offsets, float* ws, int64_t* out, int64_t* ids, int64_t* positions, int* ctx_lens,
@@ -312,19 +312,29 @@ void gelu_tanh(torch::Tensor out, torch::Tensor x) {
   launch_gelu(out.data_ptr(), x.data_ptr(), x.numel(), cur_stream());
 }
 
-void sample(torch::Tensor out, torch::Tensor logits, torch::Tensor temperature, torch::Tensor top_p,
-            torch::Tensor top_k, torch::Tensor seeds, torch::Tensor offsets, torch::Tensor ws) {
-  check_type(out, torch::kInt64, "out");
+// What sample and sample_advance ask alike of the token vector (`tok_name`: its name in the caller),
+// the logits, the per-row parameters and the workspace. Returns the batch; *bf = bf16 logits.
+int64_t check_sample_operands(const torch::Tensor& tok, const char* tok_name, const torch::Tensor& logits,
+                              const torch::Tensor& temperature, const torch::Tensor& top_p,
+                              const torch::Tensor& top_k, const torch::Tensor& seeds, const torch::Tensor& offsets,
+                              const torch::Tensor& ws, bool* bf) {
+  check_type(tok, torch::kInt64, tok_name);
   check_type(ws, torch::kFloat32, "sample workspace");
   TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1, "logits must be [B, V] row-major");
-  const bool bf = logits.scalar_type() == torch::kBFloat16;
-  TORCH_CHECK(bf || logits.scalar_type() == torch::kFloat32, "logits must be bf16 or fp32");
-  const int64_t B = logits.size(0);
+  *bf = logits.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(*bf || logits.scalar_type() == torch::kFloat32, "logits must be bf16 or fp32");
   check_type(temperature, torch::kFloat32, "temperature");
   check_type(top_p, torch::kFloat32, "top_p");
   check_type(top_k, torch::kInt32, "top_k");
   check_type(seeds, torch::kInt64, "seeds");
   check_type(offsets, torch::kInt64, "offsets");
+  return logits.size(0);
+}
+
+void sample(torch::Tensor out, torch::Tensor logits, torch::Tensor temperature, torch::Tensor top_p,
+            torch::Tensor top_k, torch::Tensor seeds, torch::Tensor offsets, torch::Tensor ws) {
+  bool bf;
+  const int64_t B = check_sample_operands(out, "out", logits, temperature, top_p, top_k, seeds, offsets, ws, &bf);
   TORCH_CHECK(out.numel() >= B && temperature.numel() >= B && top_p.numel() >= B && top_k.numel() >= B &&
                   seeds.numel() >= B && offsets.numel() >= B,
               "sampling parameter vectors shorter than the batch");
@@ -332,7 +342,7 @@ void sample(torch::Tensor out, torch::Tensor logits, torch::Tensor temperature, 
   const int rc = launch_sample(out.data_ptr<int64_t>(), logits.data_ptr(), bf, (int)B, (int)logits.size(1),
                                logits.stride(0), temperature.data_ptr<float>(), top_p.data_ptr<float>(),
                                top_k.data_ptr<int>(), seeds.data_ptr<int64_t>(), offsets.data_ptr<int64_t>(),
-                               ws.data_ptr<float>(), cur_stream(), nullptr);
+                               ws.data_ptr<float>(), cur_stream());
   TORCH_CHECK(rc == 0, "sample: rc=", rc);
 }
 
@@ -343,17 +353,8 @@ void sample_advance(torch::Tensor tok, torch::Tensor logits, torch::Tensor tempe
                     torch::Tensor out, torch::Tensor ids, torch::Tensor positions, torch::Tensor ctx_lens,
                     torch::Tensor step, torch::Tensor slots, torch::Tensor res, torch::Tensor block_tables,
                     torch::Tensor embed, int64_t block_size) {
-  check_type(tok, torch::kInt64, "tok");
-  check_type(ws, torch::kFloat32, "sample workspace");
-  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1, "logits must be [B, V] row-major");
-  const bool bf = logits.scalar_type() == torch::kBFloat16;
-  TORCH_CHECK(bf || logits.scalar_type() == torch::kFloat32, "logits must be bf16 or fp32");
-  const int64_t B = logits.size(0);
-  check_type(temperature, torch::kFloat32, "temperature");
-  check_type(top_p, torch::kFloat32, "top_p");
-  check_type(top_k, torch::kInt32, "top_k");
-  check_type(seeds, torch::kInt64, "seeds");
-  check_type(offsets, torch::kInt64, "offsets");
+  bool bf;
+  const int64_t B = check_sample_operands(tok, "tok", logits, temperature, top_p, top_k, seeds, offsets, ws, &bf);
   check_type(out, torch::kInt64, "out");
   check_type(ids, torch::kInt64, "ids");
   check_type(positions, torch::kInt64, "positions");

@@ -12,37 +12,22 @@
 //
 // Everything the next replay needs stays on the device, so a hipGraph replay takes no host
 // input. One workgroup per batch row; the embedding row copy is 16 B per lane.
-#include "common.h"
+#include "step_core.h"
 
 namespace {
-__global__ void __launch_bounds__(256) decode_prep_kernel(
-    int64_t* __restrict__ slots, int64_t* __restrict__ offsets, uint16_t* __restrict__ res,
-    const int64_t* __restrict__ ids, const int64_t* __restrict__ positions, const int* __restrict__ block_tables,
-    const uint16_t* __restrict__ embed, int max_blocks, int BS, int H, int64_t vocab) {
+using rt::PrepArgs;
+
+__global__ void __launch_bounds__(256) decode_prep_kernel(const int64_t* __restrict__ ids,
+                                                          const int64_t* __restrict__ positions, PrepArgs pa) {
   const int b = blockIdx.x;
   const int64_t pos = positions[b];
   if (threadIdx.x == 0) {
-    const int64_t bi = pos / BS;   // past the table: a slot that is never written
-    const int64_t blk = bi < max_blocks ? block_tables[(size_t)b * max_blocks + bi] : 0;
-    slots[b] = blk * BS + pos % BS;
-    offsets[b] = pos + 1;
+    pa.slots[b] = rt::kv_slot(pa, rt::kv_block(pa, b, pos), pos);
+    pa.offsets[b] = pos + 1;
   }
-  int64_t tok = ids[b];
-  tok = tok < 0 ? 0 : (tok >= vocab ? vocab - 1 : tok);
-  const uint4* src = reinterpret_cast<const uint4*>(embed + (size_t)tok * H);
-  uint4* dst = reinterpret_cast<uint4*>(res + (size_t)b * H);
-  for (int i = threadIdx.x; i < H / 8; i += blockDim.x) dst[i] = src[i];
+  const int64_t tok = ids[b];
+  for (int j = threadIdx.x; j < pa.H / 8; j += blockDim.x) rt::embed_piece(pa, b, tok, j);
 }
-
-struct PrepArgs {   // next-step prep (all null: advance only)
-  int64_t* slots;
-  int64_t* offsets;
-  uint16_t* res;
-  const int* block_tables;
-  const uint16_t* embed;
-  int max_blocks, BS, H;
-  int64_t vocab;
-};
 
 __global__ void __launch_bounds__(256) decode_advance_kernel(int64_t* __restrict__ out, int64_t* __restrict__ ids,
                                                              int64_t* __restrict__ positions, int* __restrict__ ctx_lens,
@@ -56,21 +41,16 @@ __global__ void __launch_bounds__(256) decode_advance_kernel(int64_t* __restrict
     const int64_t p = positions[b] + 1;
     positions[b] = p;
     ctx_lens[b] += 1;
-    if (pa.slots != nullptr) {   // past the table (a turn's last step) the slot is never used
-      const int64_t bi = p / pa.BS;
-      const int64_t blk = bi < pa.max_blocks ? pa.block_tables[(size_t)b * pa.max_blocks + bi] : 0;
-      pa.slots[b] = blk * pa.BS + p % pa.BS;
+    if (pa.slots != nullptr) {
+      pa.slots[b] = rt::kv_slot(pa, rt::kv_block(pa, b, p), p);
       pa.offsets[b] = p + 1;
     }
   }
   if (pa.res != nullptr) {       // next step's embedding rows, 16 B per lane
     const int row8 = pa.H / 8;
     for (int i = threadIdx.x; i < B * row8; i += blockDim.x) {
-      const int b = i / row8, j = i - b * row8;
-      int64_t tok = next[b];
-      tok = tok < 0 ? 0 : (tok >= pa.vocab ? pa.vocab - 1 : tok);
-      reinterpret_cast<uint4*>(pa.res)[(size_t)b * row8 + j] =
-          reinterpret_cast<const uint4*>(pa.embed)[(size_t)tok * row8 + j];
+      const int b = i / row8;
+      rt::embed_piece(pa, b, next[b], i - b * row8);
     }
   }
   __syncthreads();  // every lane has read *step before lane 0 bumps it
@@ -82,9 +62,9 @@ int launch_decode_prep(int64_t* slots, int64_t* offsets, void* res, const int64_
                        const int* block_tables, const void* embed, int B, int max_blocks, int BS, int H,
                        int64_t vocab, hipStream_t stream) {
   if (B <= 0) return 0;
-  if (H % 8) return -1;
-  hipLaunchKernelGGL(decode_prep_kernel, dim3(B), dim3(256), 0, stream, slots, offsets, (uint16_t*)res, ids,
-                     positions, block_tables, (const uint16_t*)embed, max_blocks, BS, H, vocab);
+  const PrepArgs pa{slots, offsets, (uint16_t*)res, block_tables, (const uint16_t*)embed, max_blocks, BS, H, vocab};
+  if (!rt::prep_args_ok(pa)) return -1;
+  hipLaunchKernelGGL(decode_prep_kernel, dim3(B), dim3(256), 0, stream, ids, positions, pa);
   return 0;
 }
 
@@ -93,12 +73,11 @@ int launch_decode_advance(int64_t* out, int64_t* ids, int64_t* positions, int* c
                           const int* block_tables, const void* embed, int max_blocks, int BS, int H, int64_t vocab,
                           hipStream_t stream) {
   if (B <= 0) return 0;
-  const bool prep = res != nullptr;
-  if (prep && (slots == nullptr || offsets == nullptr || block_tables == nullptr || embed == nullptr || H % 8 ||
-               BS <= 0 || max_blocks <= 0 || vocab <= 0))
-    return -1;
-  const PrepArgs pa{prep ? slots : nullptr, prep ? offsets : nullptr, (uint16_t*)res, block_tables,
-                    (const uint16_t*)embed, max_blocks, BS, H, vocab};
+  PrepArgs pa{};                 // no `res`: advance only
+  if (res != nullptr) {
+    pa = PrepArgs{slots, offsets, (uint16_t*)res, block_tables, (const uint16_t*)embed, max_blocks, BS, H, vocab};
+    if (!rt::prep_args_ok(pa)) return -1;
+  }
   hipLaunchKernelGGL(decode_advance_kernel, dim3(1), dim3(256), 0, stream, out, ids, positions, ctx_lens, step, next,
                      B, max_steps, pa);
   return 0;

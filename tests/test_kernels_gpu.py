@@ -437,6 +437,41 @@ def test_sample_top_p_nucleus():
     assert hits <= {0, 1} and len(hits) == 2
 
 
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("V", [5, 37, 1003])
+def test_sample_unaligned_rows_and_short_vocab(V, dtype):
+    """Rows off 16 bytes with a stride that is no multiple of 16 bytes (the non-vector kernels) and
+    their aligned twin with a ragged tail (the vector kernels), at vocabularies below one vector
+    per lane: V = 5 is one chunk with no full vector, V = 37 leaves 27 of the 32 chunks empty,
+    V = 1003 has a ragged last chunk and k = 100 > 64 runs the two-level histogram with top-p
+    inside it. For these inputs the fp64 reference's margins (top two allowed scores >= 0.075
+    apart, top_p * Z >= 2.5e-4 * Z from every cumulative-mass boundary, no tie at a greedy row's
+    maximum) are far outside fp32 rounding: every draw must equal the reference."""
+    B = 6
+    big = (torch.randn(B, V + 9, generator=torch.Generator().manual_seed(900 + V)) * 2.0).to(torch.bfloat16).to(dtype)
+    vals = big[:, 1:1 + V]
+    unaligned = big.to(DEV)[:, 1:1 + V]
+    pad = torch.zeros(B, (V + 15) // 8 * 8, dtype=dtype)
+    pad[:, :V] = vals
+    aligned = pad.to(DEV)[:, :V]
+    assert unaligned.data_ptr() % 16 != 0
+    assert aligned.data_ptr() % 16 == 0 and (aligned.stride(0) * aligned.element_size()) % 16 == 0
+    temp = torch.tensor([0.0, 0.8, 0.8, 0.8, 0.8, 0.8])
+    top_p = torch.tensor([1.0, 1.0, 0.6, 1.0, 0.7, 0.9])
+    top_k = torch.tensor([0, 0, 0, 3, 4, 100], dtype=torch.int32)
+    ws_u, ws_a = ops.sample_workspace(B, DEV), ops.sample_workspace(B, DEV)
+    for rep in range(4):
+        seeds = torch.arange(B, dtype=torch.int64) * 613 + rep
+        offs = torch.arange(B, dtype=torch.int64) + 50 * rep
+        exp = ref.sample(vals, temp, top_p, top_k, seeds, offs)
+        par = [t.to(DEV) for t in (temp, top_p, top_k, seeds, offs)]
+        got_u = ops.sample(unaligned, *par, ws=ws_u).cpu()
+        got_a = ops.sample(aligned, *par, ws=ws_a).cpu()
+        assert torch.equal(got_u, exp), (rep, got_u, exp)
+        assert torch.equal(got_a, exp), (rep, got_a, exp)
+        assert torch.equal(got_u, got_a), (rep, got_u, got_a)
+
+
 
 @pytest.mark.parametrize("mode", ["greedy", "top_p", "top_k"])
 def test_sample_advance_equals_sample_then_advance(mode):
