@@ -166,7 +166,9 @@ void rope_and_cache(torch::Tensor q_out, torch::Tensor qkv, torch::Tensor positi
   const int64_t T = qkv.size(0);
   TORCH_CHECK(qkv.size(1) == (Hq + 2 * Hkv) * D, "qkv width mismatch");
   TORCH_CHECK(positions.numel() == T && slots.numel() == T && q_out.numel() == T * Hq * D, "token count mismatch");
-  TORCH_CHECK(D % 8 == 0, "head_dim must be a multiple of 8");
+  // kc_elem (common.h) addresses K as [D/32][BS][32]: with D % 32 != 0 the last chunk of a head
+  // would land in the next head's keys
+  TORCH_CHECK(D > 0 && D % 32 == 0, "head_dim must be a multiple of 32 (chunk-major K cache layout [D/32][BS][32])");
   const bool rope = cos_sin.numel() > 0;
   if (rope) {
     check_type(cos_sin, torch::kFloat32, "cos_sin");
@@ -488,7 +490,9 @@ void skinny_gemm_rope(torch::Tensor q_out, torch::Tensor x, torch::Tensor Ws, in
   TORCH_CHECK(x.dim() == 2 && Ws.dim() == 2 && x.size(1) == Ws.size(1), "skinny_gemm_rope: x [M,K], Ws [N,K]");
   const int64_t M = x.size(0), K = x.size(1);
   TORCH_CHECK(M >= 1 && M <= 32 && K % 32 == 0, "skinny_gemm_rope: 1 <= M <= 32, K % 32 == 0");
-  TORCH_CHECK(Ws.size(0) == (Hq + 2 * Hkv) * D && D % 16 == 0, "skinny_gemm_rope: Ws must be [(Hq+2Hkv)*D, K]");
+  TORCH_CHECK(Ws.size(0) == (Hq + 2 * Hkv) * D, "skinny_gemm_rope: Ws must be [(Hq+2Hkv)*D, K]");
+  TORCH_CHECK(D > 0 && D % 32 == 0,
+              "skinny_gemm_rope: head_dim must be a multiple of 32 (chunk-major K cache layout [D/32][BS][32])");
   const float* bp = rope_operands("skinny_gemm_rope", q_out, x, M, positions, cos_sin, k_cache, v_cache, slots, Hq,
                                   Hkv, D, bias);
   const auto addo = add_operands(x, pro, x2, xout);
@@ -757,7 +761,9 @@ void skinny_gemm_rope_fp8(torch::Tensor q_out, torch::Tensor x, torch::Tensor Wq
   TORCH_CHECK(x.dim() == 2, "skinny_gemm_rope_fp8: x [M, K]");
   const int64_t M = x.size(0), K = x.size(1);
   check_fp8_weight(Wq, scale, (Hq + 2 * Hkv) * D, K, "skinny_gemm_rope_fp8");
-  TORCH_CHECK(M >= 1 && M <= 16 && D % 16 == 0, "skinny_gemm_rope_fp8: 1 <= M <= 16, D % 16 == 0");
+  TORCH_CHECK(M >= 1 && M <= 16, "skinny_gemm_rope_fp8: 1 <= M <= 16");
+  TORCH_CHECK(D > 0 && D % 32 == 0,
+              "skinny_gemm_rope_fp8: head_dim must be a multiple of 32 (chunk-major K cache layout [D/32][BS][32])");
   TORCH_CHECK(pro == 0 || pro == 1, "skinny_gemm_rope_fp8: prologue PLAIN or NORM");
   const float* bp = rope_operands("skinny_gemm_rope_fp8", q_out, x, M, positions, cos_sin, k_cache, v_cache, slots,
                                   Hq, Hkv, D, bias);

@@ -254,7 +254,8 @@ int launch_gemm(int wt, void* out, const void* x, const void* Ws, const float* w
   if (epi == EPI_ROPE) {
     if (rope == nullptr) return -3;
     re = *static_cast<const RopeEpi*>(rope);
-    if (re.D % 16 || N != (re.Hq + 2 * re.Hkv) * re.D) return -4;
+    // D % 32: the K write goes through kc_elem ([D/32][BS][32] chunks)
+    if (re.D <= 0 || re.D % 32 || N != (re.Hq + 2 * re.Hkv) * re.D) return -4;
   }
   const SkinnyPlan pl =
       plan_skinny_gemm(wt, M, N, K, pro, epi, device_cus(), split_ws != nullptr, split_ws_ints, split_mode, knobs());

@@ -36,17 +36,35 @@ __global__ void __launch_bounds__(1024) norm_kernel(uint16_t* __restrict__ out, 
           r[j] = (short)rt::f2bf(f);
         }
         v[i][j] = f;
-        s1 += f;
-        ss += f * f;
+        if constexpr (LN) s1 += f;
+        else ss += f * f;
       }
       if constexpr (ADD) *reinterpret_cast<rt::short8*>(rr + c * 8) = r;
     }
   }
-  float mean = 0.f, inv;
+  float inv;
   if constexpr (LN) {
-    mean = rt::block_sum(s1, scratch) / H;
-    float var = rt::block_sum(ss, scratch) / H - mean * mean;
-    inv = rsqrtf(fmaxf(var, 0.f) + eps);
+    // Two passes over the registers: E[x^2] - mean^2 loses the variance of a row whose mean is
+    // large against its spread (3000 +- 16: fp32 x^2 ~ 9e6 carries an error of ~1 against a
+    // variance of 256). The mean is kept as hi + lo (lo = the division's remainder, exact through
+    // the fma): its fp32 rounding alone, |mean| 2^-25, is an error of mean / sigma * 2^-25 in
+    // every normalized value. v becomes x - mean.
+    const float s = rt::block_sum(s1, scratch);
+    const float mean = s / H;
+    const float mean_lo = fmaf(-mean, (float)H, s) / H;
+    float sd = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i) {
+      if ((int)(threadIdx.x + i * blockDim.x) < nchunk) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float d = (v[i][j] - mean) - mean_lo;
+          v[i][j] = d;
+          sd += d * d;
+        }
+      }
+    }
+    inv = rsqrtf(rt::block_sum(sd, scratch) / H + eps);
   } else {
     inv = rsqrtf(rt::block_sum(ss, scratch) / H + eps);
   }
@@ -61,7 +79,7 @@ __global__ void __launch_bounds__(1024) norm_kernel(uint16_t* __restrict__ out, 
       rt::short8 o;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        float y = (v[i][j] - mean) * inv * rt::bf2f((uint16_t)wv[j]);
+        float y = v[i][j] * inv * rt::bf2f((uint16_t)wv[j]);
         if constexpr (LN) y += rt::bf2f((uint16_t)bv[j]);
         o[j] = (short)rt::f2bf(y);
       }

@@ -68,6 +68,7 @@ __global__ void __launch_bounds__(256) rope_cache_kernel(
 }
 }  // namespace
 
+// D must be a multiple of 32 (the K chunks; checked by the binding).
 void launch_rope_cache(void* q_out, const void* qkv, const int64_t* positions, const float* cos_sin,
                        void* k_cache, void* v_cache, const int64_t* slots, int T, int Hq, int Hkv, int D, int BS,
                        int64_t qkv_stride, bool rope, hipStream_t stream) {
