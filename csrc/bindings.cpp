@@ -59,6 +59,10 @@ int launch_decode_advance(int64_t* out, int64_t* ids, int64_t* positions, int* c
                           const int64_t* next, int B, int max_steps, int64_t* slots, int64_t* offsets, void* res,
                           const int* block_tables, const void* embed, int max_blocks, int BS, int H, int64_t vocab,
                           hipStream_t stream);
+int launch_logit_proc(void* logits, int dtype, int B, int V, int64_t ld, const int* hist, int hist_cap,
+                      const int* hist_len, const int* reply_from, const float* rp, const int* last_n, const float* pp,
+                      const float* fp, const int* bias_tok, const float* bias_val, const int* bias_n, int bias_cap,
+                      const int64_t* out, const int64_t* step, int max_steps, int out_ld, hipStream_t stream);
 int oneshot_create(int world, int rank, int cap_elems, char* handles);
 int oneshot_open(int id, const char* all_handles);
 int oneshot_capacity(int id);
@@ -661,6 +665,55 @@ void paging_guard(torch::Tensor block_tables, torch::Tensor ctx_lens, c10::optio
   TORCH_CHECK(rc == 0, "paging_guard: rc=", rc);
 }
 
+// Logit processors (csrc/logit_proc.hip): bias, repetition, frequency / presence penalties applied in
+// place to logits [B, V] (row stride >= V) from hist ++ out[0:*step]; capturable.
+void logit_proc(torch::Tensor logits, torch::Tensor hist, torch::Tensor hist_len, torch::Tensor reply_from,
+                torch::Tensor rp, torch::Tensor last_n, torch::Tensor pp, torch::Tensor fp, torch::Tensor bias_tok,
+                torch::Tensor bias_val, torch::Tensor bias_n, c10::optional<torch::Tensor> out,
+                c10::optional<torch::Tensor> step) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1, "logit_proc: logits must be [B, V] rows");
+  const auto st = logits.scalar_type();
+  TORCH_CHECK(st == torch::kBFloat16 || st == torch::kFloat32, "logit_proc: logits must be bfloat16 or float32");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  const int64_t ld = B > 1 ? logits.stride(0) : V;
+  TORCH_CHECK(ld >= V && V < (int64_t(1) << 31), "logit_proc: row stride must be >= V");
+  check_type(hist, torch::kInt32, "hist");
+  check_type(hist_len, torch::kInt32, "hist_len");
+  check_type(reply_from, torch::kInt32, "reply_from");
+  check_type(rp, torch::kFloat32, "rp");
+  check_type(last_n, torch::kInt32, "last_n");
+  check_type(pp, torch::kFloat32, "pp");
+  check_type(fp, torch::kFloat32, "fp");
+  check_type(bias_tok, torch::kInt32, "bias_tok");
+  check_type(bias_val, torch::kFloat32, "bias_val");
+  check_type(bias_n, torch::kInt32, "bias_n");
+  TORCH_CHECK(hist.dim() == 2 && hist.size(0) >= B && hist_len.numel() >= B && reply_from.numel() >= B &&
+                  rp.numel() >= B && last_n.numel() >= B && pp.numel() >= B && fp.numel() >= B && bias_n.numel() >= B,
+              "logit_proc: per-row tensors must cover the batch");
+  TORCH_CHECK(bias_tok.dim() == 2 && bias_tok.size(0) >= B && bias_val.sizes() == bias_tok.sizes(),
+              "logit_proc: bias_tok / bias_val [B, n]");
+  const int64_t* op = nullptr;
+  const int64_t* sp = nullptr;
+  int max_steps = 0, out_ld = 0;
+  if (step.has_value() && step->defined()) {
+    TORCH_CHECK(out.has_value() && out->defined(), "logit_proc: step needs out");
+    check_type(*out, torch::kInt64, "out");
+    check_type(*step, torch::kInt64, "step");
+    TORCH_CHECK(out->dim() == 2 && out->size(1) >= B && step->numel() >= 1, "logit_proc: out [steps, B], step [1]");
+    op = out->data_ptr<int64_t>();
+    sp = step->data_ptr<int64_t>();
+    max_steps = (int)out->size(0);
+    out_ld = (int)out->size(1);
+  }
+  const int rc = launch_logit_proc(logits.data_ptr(), st == torch::kBFloat16 ? 0 : 1, (int)B, (int)V, ld,
+                                   hist.data_ptr<int>(), (int)hist.size(1), hist_len.data_ptr<int>(),
+                                   reply_from.data_ptr<int>(), rp.data_ptr<float>(), last_n.data_ptr<int>(),
+                                   pp.data_ptr<float>(), fp.data_ptr<float>(), bias_tok.data_ptr<int>(),
+                                   bias_val.data_ptr<float>(), bias_n.data_ptr<int>(), (int)bias_tok.size(1), op, sp,
+                                   max_steps, out_ld, cur_stream());
+  TORCH_CHECK(rc == 0, "logit_proc: unsupported configuration (rc=", rc, ")");
+}
+
 void shuffle_weight(torch::Tensor Ws, torch::Tensor W, c10::optional<torch::Tensor> gamma, int64_t rope_heads,
                     int64_t head_dim, bool swiglu) {
   check_bf16(Ws, "Ws");
@@ -856,5 +909,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("sample", &sample);
   m.def("sample_advance", &sample_advance);
   m.def("sample_workspace_floats", &sample_workspace_floats);
+  m.def("logit_proc", &logit_proc, py::arg("logits"), py::arg("hist"), py::arg("hist_len"), py::arg("reply_from"),
+        py::arg("rp"), py::arg("last_n"), py::arg("pp"), py::arg("fp"), py::arg("bias_tok"), py::arg("bias_val"),
+        py::arg("bias_n"), py::arg("out") = py::none(), py::arg("step") = py::none());
   m.attr("arch") = "gfx950";
 }

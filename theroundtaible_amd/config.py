@@ -10,7 +10,9 @@ object that tells the local engine how to host that knight, and a top-level
 
     "engine": {"default_model": "llama3-8b", "dtype": "bf16", "weights": "random:0",
                "kv_block_size": 32, "max_new_tokens": 512, "temperature": 0.7,
-               "top_p": 0.95, "top_k": 0, "seed": 0, "stop_on_consensus": true},
+               "top_p": 0.95, "top_k": 0, "seed": 0, "stop_on_consensus": true,
+               "repetition_penalty": 1.0, "repeat_last_n": 64, "presence_penalty": 0.0,
+               "frequency_penalty": 0.0, "logit_bias": null},
     "adapter_config": {"claude-cli": {"command": "claude", "args": [],
                                       "engine": {"model": "llama3-8b", "gpus": [0], "tp": 1}}}
 
@@ -46,6 +48,12 @@ ENGINE_DEFAULTS: Dict[str, Any] = {
     "stop_on_consensus": True,
     "ignore_eos": False,
     "kv_cache_fraction": 0.85,
+    # logit processors (engine/sampler.py), neutral: logit_bias is {"<token id>": bias} or null
+    "repetition_penalty": 1.0,
+    "repeat_last_n": 64,
+    "presence_penalty": 0.0,
+    "frequency_penalty": 0.0,
+    "logit_bias": None,
 }
 
 
@@ -135,6 +143,26 @@ def engine_settings(config: RoundtableConfig, adapter_id: str) -> Dict[str, Any]
         out["model"] = resolve_model_name(ac.get("model") if isinstance(ac, dict) else None,
                                           out["default_model"])
     out["weight_quant"] = resolve_weight_quant(out.get("weight_quant"))
+    return out
+
+
+def processor_settings(st: Dict[str, Any]) -> Dict[str, Any]:
+    """The logit-processor keys of an engine settings block as SamplingParams arguments (JSON
+    writes ``logit_bias`` token ids as strings); ConfigError for a value outside their ranges."""
+    from .engine.sampler import SamplingParams
+    bias = st.get("logit_bias")
+    try:
+        if bias is not None and not isinstance(bias, dict):
+            raise ValueError("logit_bias must be an object of token id -> bias")
+        out = {"repetition_penalty": float(st.get("repetition_penalty", 1.0)),
+               "repeat_last_n": int(st.get("repeat_last_n", 64)),
+               "presence_penalty": float(st.get("presence_penalty", 0.0)),
+               "frequency_penalty": float(st.get("frequency_penalty", 0.0)),
+               "logit_bias": {int(k): float(v) for k, v in bias.items()} if bias else None}
+        SamplingParams(**out).check_processors()
+    except (TypeError, ValueError) as e:
+        raise ConfigError(f"engine sampling settings: {e}",
+                          hint="penalties in [-2, 2], repetition_penalty > 0, at most 300 biases in [-100, 100].")
     return out
 
 

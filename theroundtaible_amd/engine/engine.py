@@ -817,6 +817,8 @@ class Engine:
             reused.append(n)
         deltas = [ids[n:] for ids, n in zip(targets, reused)]
         logits = self._prefill_turns(shared_items, seqs, deltas)
+        for sq in seqs:     # the reply starts after the prompt; the chunked decode carries it across its calls
+            sq.reply_start = sq.length
         first = self._sample_host(logits, seqs, turns).tolist()
         ms = (time.perf_counter() - t0) * 1e3
         self.stats["prefill_tokens"] += sum(len(d) for d in deltas) + sum(shared_pre.values())
@@ -871,13 +873,17 @@ class Engine:
                       t.timeout_s) for t in turns]
         eos = self.tokenizer.stop_ids
         t0 = time.perf_counter()
+        # where each reply began: set by start_turns; a sequence decoded without it starts its reply at ``last``
+        starts = [sq.length if sq.reply_start is None else min(sq.reply_start, sq.length) for sq in seqs]
         runner = self._agreed_graph(len(seqs), max(sq.length for sq in seqs) + steps + 1, groups is not None,
-                                    self.dist_greedy(chunk))
+                                    self.dist_greedy(chunk), processors=self.wants_processors(chunk))
         with trace.range(f"decode chunk B={len(seqs)} steps={steps}"):
             if runner is not None:
-                toks = runner.run(self, seqs, chunk, first, steps + 1, time.perf_counter() + 1e9, eos, groups)
+                toks = runner.run(self, seqs, chunk, first, steps + 1, time.perf_counter() + 1e9, eos, groups,
+                                  reply_starts=starts)
             else:
-                toks = self._decode_eager(seqs, chunk, first, steps + 1, time.perf_counter() + 1e9, eos, groups)
+                toks = self._decode_eager(seqs, chunk, first, steps + 1, time.perf_counter() + 1e9, eos, groups,
+                                          reply_starts=starts)
         out = []
         for sq, tk, f in zip(seqs, toks, last):
             new = list(tk[1:steps + 1])
@@ -895,7 +901,16 @@ class Engine:
         top_k = torch.tensor([t.params.top_k for t in turns], dtype=torch.int32, device=dev)
         seeds = torch.tensor([t.params.seq_seed(t.seq_key) for t in turns], dtype=torch.int64, device=dev)
         offs = torch.tensor([s.length for s in seqs], dtype=torch.int64, device=dev)
-        return ops.sample(logits.contiguous(), temp, top_p, top_k, seeds, offs)
+        logits = logits.contiguous()
+        if self.wants_processors(turns):    # the first token obeys bans and penalties too (no reply yet)
+            proc = ops.LogitProc(B, dev).fill([(s.tokens, s.length, t.params) for s, t in zip(seqs, turns)])
+            ops.apply_logit_processors(logits, proc)
+        return ops.sample(logits, temp, top_p, top_k, seeds, offs)
+
+    @staticmethod
+    def wants_processors(turns: Sequence[Turn]) -> bool:
+        """Some row of the batch asks for a logit processor (bias / repetition / frequency / presence)."""
+        return any(t.params.has_processors() for t in turns)
 
     # ---- decode -------------------------------------------------------------------------------------
     def decode(self, seqs: Sequence[SeqState], turns: Sequence[Turn], first: torch.Tensor,
@@ -909,7 +924,8 @@ class Engine:
         for s, n in zip(seqs, max_new):
             self.kv.ensure_capacity(s, s.length + steps)
         eos = self.tokenizer.stop_ids
-        runner = self._agreed_graph(B, max(s.length for s in seqs) + steps, groups is not None, self.dist_greedy(turns))
+        runner = self._agreed_graph(B, max(s.length for s in seqs) + steps, groups is not None, self.dist_greedy(turns),
+                                    processors=self.wants_processors(turns))
         with trace.range(f"decode B={B} steps={steps}"):
             if runner is not None:
                 toks = runner.run(self, seqs, turns, first, steps, deadline, eos, groups)
@@ -953,7 +969,8 @@ class Engine:
         t, _ = ops.decode_groups(labels, shb, self.model.n_heads // self.model.n_kv_heads)
         return t
 
-    def _decode_eager(self, seqs, turns, first, steps, deadline, eos, groups=None) -> List[List[int]]:
+    def _decode_eager(self, seqs, turns, first, steps, deadline, eos, groups=None,
+                      reply_starts=None) -> List[List[int]]:
         dev = self.device
         B = len(seqs)
         cur = first.clone()
@@ -976,6 +993,9 @@ class Engine:
         gt = self.group_table(groups, B)
         gt = gt.to(dev) if gt is not None and self.on_gpu else None
         dist_greedy = self.dist_greedy(turns)
+        # logit processors: the same op as the captured step, from host history only
+        proc = ops.LogitProc(B, dev) if self.wants_processors(turns) else None
+        starts = reply_starts if reply_starts is not None else [s.length for s in seqs]
         for step in range(1, steps):
             pos = list(lens)
             slots = [s.blocks[p // self.kv.block_size] * self.kv.block_size + p % self.kv.block_size
@@ -985,6 +1005,10 @@ class Engine:
                             num_splits=splits, workspace=ws, groups=gt, local_logits=dist_greedy)
             logits = self.model.forward(cur.to(dev), torch.tensor(pos, dtype=torch.int64, device=dev), self.kv, meta)
             offs = torch.tensor([p + 1 for p in pos], dtype=torch.int64, device=dev)
+            if proc is not None:
+                logits = logits.contiguous()
+                proc.fill([(s.tokens + o, r, t.params) for s, o, r, t in zip(seqs, out, starts, turns)])
+                ops.apply_logit_processors(logits, proc)
             if dist_greedy:
                 cur = self.tp.greedy_gather(logits, self.cfg.vocab)
             else:
@@ -1026,6 +1050,8 @@ class Engine:
         there the logits go through K9's one-shot gather and the sampler takes the argmax."""
         if self.tp.size == 1 or not all(t.params.temperature <= 0 for t in turns):
             return False
+        if self.wants_processors(turns):    # processors need full rows: the (value, id) gather never sees them
+            return False
         return not (self.on_gpu and self.ecfg.use_graphs and self.tp.backend() != "nccl")
 
     def k9_only_step(self) -> bool:
@@ -1034,7 +1060,7 @@ class Engine:
         os_ = self.tp.oneshot
         return os_ is not None and bool(getattr(os_, "gather_ok", False))
 
-    def _agreed_graph(self, B: int, max_ctx: int, grouped: bool, dist_greedy: bool):
+    def _agreed_graph(self, B: int, max_ctx: int, grouped: bool, dist_greedy: bool, processors: bool = False):
         """The captured decode step, or None (eager). A capture that fails on ANY rank of a
         tensor-parallel group sends EVERY rank to eager decode: a rank replaying a graph whose K9
         calls no peer issues would wait out each poll bound. The group agrees twice, only when the
@@ -1042,18 +1068,23 @@ class Engine:
         a cached replay costs no host round trip): after the graph's buffers are allocated (where
         an out-of-memory rank fails, before any K9 call) and after the capture itself, whose eager
         warm-up runs issue K9 calls — a rank failing in there leaves the counters apart, so the
-        fallback re-agrees them (:meth:`_resync_k9`)."""
+        fallback re-agrees them (:meth:`_resync_k9`).
+
+        ``processors``: the variant whose step applies the logit processors before K6. It is cached
+        beside the plain graph under ``(key, "proc")``; batches without processors never see it."""
         if not (self.on_gpu and self.ecfg.use_graphs):
             return None
         key = self._graph_key(B, grouped, dist_greedy)
-        g = self.graphs.get(key)
+        ckey = (key, "proc") if processors else key
+        g = self.graphs.get(ckey)
         if g is not None:
             return g
         from .graphs import DecodeGraph
         g, err = None, None
         try:
-            with failsafe.stage("capture"):
-                g = DecodeGraph(self, key[0], key[1], grouped=grouped, dist_greedy=dist_greedy, capture=False)
+            with failsafe.stage("capture"):     # the plain graph is constructed exactly as before the flag existed
+                g = DecodeGraph(self, key[0], key[1], grouped=grouped, dist_greedy=dist_greedy, capture=False,
+                                **({"processors": True} if processors else {}))
         except RuntimeError as e:   # out of memory for the graph's static buffers
             err = e
         failed = self.tp.any_rank(err is not None) if self.tp.size > 1 else err is not None
@@ -1078,20 +1109,24 @@ class Engine:
             if calls_issued:
                 self._resync_k9()
             return None
-        self.graphs[key] = g
+        self.graphs[ckey] = g
+        self.stats["graph_captures"] = self.stats.get("graph_captures", 0) + 1
         return g
 
     def _graph_key(self, B: int, grouped: bool, dist_greedy: bool) -> Tuple[int, int, bool, bool]:
         bucket = next((b for b in BATCH_BUCKETS if b >= B), B)
         return (bucket, ops.decode_splits(bucket, self.model.n_kv_heads, grouped=grouped), grouped, dist_greedy)
 
-    def _graph_for(self, B: int, max_ctx: int, grouped: bool = False, dist_greedy: bool = False) -> "DecodeGraph":
+    def _graph_for(self, B: int, max_ctx: int, grouped: bool = False, dist_greedy: bool = False,
+                   processors: bool = False) -> "DecodeGraph":
         from .graphs import DecodeGraph
         key = self._graph_key(B, grouped, dist_greedy)
-        g = self.graphs.get(key)
+        ckey = (key, "proc") if processors else key
+        g = self.graphs.get(ckey)
         if g is None:
-            g = DecodeGraph(self, key[0], key[1], grouped=grouped, dist_greedy=dist_greedy)
-            self.graphs[key] = g
+            g = DecodeGraph(self, key[0], key[1], grouped=grouped, dist_greedy=dist_greedy, processors=processors)
+            self.graphs[ckey] = g
+            self.stats["graph_captures"] = self.stats.get("graph_captures", 0) + 1
         return g
 
 

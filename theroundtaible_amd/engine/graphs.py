@@ -55,7 +55,7 @@ def no_gc_during_capture():
 
 class DecodeGraph:
     def __init__(self, engine, bucket: int, splits: int, grouped: bool = False, dist_greedy: bool = False,
-                 capture: bool = True):
+                 capture: bool = True, processors: bool = False):
         self.engine = engine
         self.B = bucket
         self.splits = splits
@@ -92,6 +92,10 @@ class DecodeGraph:
         self.guard_err = torch.zeros(1, dtype=torch.int32, device=dev)   # debug paging guard (captured)
         self.nxt = torch.zeros(B, dtype=torch.int64, device=dev)
         self.sample_ws = ops.sample_workspace(B, dev)      # self-re-arming K6 tickets
+        # logit processors (bias / repetition / frequency / presence): a graph captured with them owns
+        # their static operands; the captured kernel reads the reply so far from ``out`` / ``step``
+        assert not (processors and dist_greedy), "the (value, id) gather never sees processed rows"
+        self.proc = ops.LogitProc(B, dev) if processors else None
         self.graph = None
         self._host_out: List[torch.Tensor] = []
         if capture:     # (Engine._agreed_graph agrees on the buffers first, then captures)
@@ -130,6 +134,9 @@ class DecodeGraph:
             logits = e.model.forward(self.input_ids, self.positions, e.kv, meta, hidden=hidden)
         else:
             logits = e.model.forward(self.input_ids, self.positions, e.kv, meta)
+        if self.proc is not None:
+            logits = logits.contiguous()
+            ops.apply_logit_processors(logits, self.proc, self.out, self.step)
         if fused and not self.dist_greedy:
             # ONE launch: K6 sampling + record / advance + the next step's slots, offsets, embeddings
             ops.sample_advance(logits.contiguous(), self.temp, self.top_p, self.top_k, self.seeds, offsets,
@@ -200,7 +207,9 @@ class DecodeGraph:
         self._reset_dummy()
 
     def run(self, engine, seqs: Sequence, turns: Sequence, first: torch.Tensor, steps: int, deadline: float,
-            eos: int, groups=None) -> List[List[int]]:
+            eos: int, groups=None, reply_starts=None) -> List[List[int]]:
+        """``reply_starts``: per sequence, the index in ``tokens + [first]`` at which its reply starts
+        (default: ``first`` is the reply's first token); only a graph with processors reads it."""
         from .engine import _finished
         B = len(seqs)
         dev = engine.device
@@ -224,6 +233,11 @@ class DecodeGraph:
         self.top_p.copy_(torch.tensor([t.params.top_p for t in turns] + [1.0] * pad, dtype=torch.float32))
         self.top_k.copy_(torch.tensor([t.params.top_k for t in turns] + [0] * pad, dtype=torch.int32))
         self.seeds.copy_(torch.tensor([t.params.seq_seed(t.seq_key) for t in turns] + [0] * pad, dtype=torch.int64))
+        first_host = first[:B].tolist()
+        if self.proc is not None:
+            starts = reply_starts if reply_starts is not None else [s.length for s in seqs]
+            self.proc.fill([(s.tokens + [f], r, t.params) for s, f, r, t in zip(seqs, first_host, starts, turns)]
+                           + [None] * pad)
         with torch.no_grad():
             self._prep()
         need_tokens = any((not t.params.ignore_eos) or t.params.stop_on_consensus for t in turns)
@@ -234,7 +248,6 @@ class DecodeGraph:
         # seen at most 2 chunks (= sync_every) late, as before; extra replays past it are
         # discarded (their K/V lies beyond the kept tokens and is truncated).
         chunk = max(1, engine.ecfg.sync_every // 2) if need_tokens else engine.ecfg.sync_every
-        first_host = first[:B].tolist()
         done_at = steps
         pending = None
         replays = engine.stats.get("graph_replays", 0)

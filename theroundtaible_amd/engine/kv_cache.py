@@ -57,6 +57,9 @@ class SeqState:
     key: str
     tokens: List[int] = field(default_factory=list)
     blocks: List[int] = field(default_factory=list)
+    # index in ``tokens`` at which the current reply starts (Engine.start_turns; None: not decoding
+    # in chunks) — the logit processors count a reply's tokens across continue_decode calls
+    reply_start: Optional[int] = None
 
     @property
     def length(self) -> int:

@@ -2,8 +2,10 @@
 from __future__ import annotations
 
 import hashlib
-from typing import Optional
+from typing import Dict, Optional
 from dataclasses import dataclass
+
+MAX_LOGIT_BIAS = 300     # OpenAI's limit; ops.LOGIT_PROC_MAX_BIAS
 
 
 @dataclass
@@ -17,6 +19,35 @@ class SamplingParams:
     stop_on_consensus: bool = True
     # teacher-forced text appended after the sampled tokens (knights/script.py scripted consensus)
     forced_tail: Optional[str] = None
+    # logit processors (csrc/logit_proc.hip), applied before temperature / top-k / top-p; all neutral
+    # by default. Order: logit_bias, repetition penalty, then frequency and presence.
+    repetition_penalty: float = 1.0     # HF / Ollama form over the last ``repeat_last_n`` tokens, prompt included
+    repeat_last_n: int = 64             # 0 = off, -1 = the cap (ops.LOGIT_PROC_WINDOW)
+    presence_penalty: float = 0.0       # OpenAI form, over the tokens of this reply
+    frequency_penalty: float = 0.0      # OpenAI form, times the token's count in this reply
+    logit_bias: Optional[Dict[int, float]] = None   # {token id: bias}, at most 300 entries in [-100, 100]
+
+    def has_processors(self) -> bool:
+        """False when every processor field is neutral: such a row is sampled exactly as before."""
+        return bool((self.repetition_penalty != 1.0 and self.repeat_last_n != 0) or self.presence_penalty != 0.0
+                    or self.frequency_penalty != 0.0 or self.logit_bias)
+
+    def check_processors(self, vocab: Optional[int] = None) -> None:
+        """ValueError for values the processors do not accept (the limits serve.py answers 400 for)."""
+        for name in ("presence_penalty", "frequency_penalty"):
+            v = getattr(self, name)
+            if not -2.0 <= float(v) <= 2.0:
+                raise ValueError(f"{name} must be in [-2, 2], got {v}")
+        if not float(self.repetition_penalty) > 0.0:
+            raise ValueError(f"repetition_penalty must be > 0, got {self.repetition_penalty}")
+        bias = self.logit_bias or {}
+        if len(bias) > MAX_LOGIT_BIAS:
+            raise ValueError(f"logit_bias has {len(bias)} entries; at most {MAX_LOGIT_BIAS} are allowed")
+        for tok, v in bias.items():
+            if not -100.0 <= float(v) <= 100.0:
+                raise ValueError(f"logit_bias[{tok}] must be in [-100, 100], got {v}")
+            if int(tok) < 0 or (vocab is not None and int(tok) >= vocab):
+                raise ValueError(f"logit_bias token id {tok} is outside the vocabulary")
 
     def seq_seed(self, seq_key: str) -> int:
         """Deterministic per (engine seed, knight): sample i of a knight depends only on (seed, knight, position)."""

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 from typing import Callable, Dict, Optional
 
-from ..config import engine_settings
+from ..config import engine_settings, processor_settings
 from ..engine.engine import EngineConfig
 from ..engine.sampler import SamplingParams
 from ..types import RoundtableConfig
@@ -102,7 +102,8 @@ class BackendFactory:
                                 top_k=int(st.get("top_k", 0)), seed=int(st.get("seed", 0)),
                                 max_new_tokens=int(st.get("max_new_tokens", 512)),
                                 ignore_eos=bool(st.get("ignore_eos", False)),
-                                stop_on_consensus=bool(st.get("stop_on_consensus", True)))
+                                stop_on_consensus=bool(st.get("stop_on_consensus", True)),
+                                **processor_settings(st))
         return EngineBackend(name, adapter_id, engine, params, lock,
                              script=ConsensusScript.from_config(st.get("scripted_consensus")))
 

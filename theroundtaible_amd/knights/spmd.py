@@ -22,7 +22,7 @@ import datetime
 import threading
 from typing import Dict, List, Tuple
 
-from ..config import engine_settings
+from ..config import engine_settings, processor_settings
 from ..engine.engine import Engine, EngineConfig
 from ..engine.sampler import SamplingParams
 from ..parallel.cluster import Cluster, load_group_for
@@ -109,7 +109,8 @@ def build_spmd_backends(config: RoundtableConfig, cluster: Cluster, ui: UI = NUL
                                 top_k=int(st.get("top_k", 0)), seed=int(st.get("seed", 0)),
                                 max_new_tokens=int(max_new_tokens or st.get("max_new_tokens", 512)),
                                 ignore_eos=bool(st.get("ignore_eos", False)),
-                                stop_on_consensus=bool(st.get("stop_on_consensus", True)))
+                                stop_on_consensus=bool(st.get("stop_on_consensus", True)),
+                                **processor_settings(st))
         local[aid] = EngineBackend(display_name(aid, config), aid, engine, params, lock,
                                    script=ConsensusScript.from_config(st.get("scripted_consensus")))
         ui.ok(f"  ✓ {k.name}: {st['model']} on rank(s) {ranks}" + (f" (tp={len(ranks)})" if len(ranks) > 1 else ""))

@@ -629,3 +629,76 @@ def sample_advance(logits: torch.Tensor, temperature: torch.Tensor, top_p: torch
     ref.decode_advance(out, ids, positions, ctx_lens, step, nxt, (slots, offsets, res, block_tables, embed,
                                                                   block_size))
     return nxt
+
+
+LOGIT_PROC_WINDOW = ref.LOGIT_PROC_WINDOW        # tokens the repetition set / the counted reply reach back
+LOGIT_PROC_MAX_BIAS = ref.LOGIT_PROC_MAX_BIAS    # logit_bias entries per row
+
+
+class LogitProc:
+    """Static per-row operands of :func:`apply_logit_processors` for a batch of ``batch`` rows, all
+    neutral until :meth:`fill`: ``hist`` [B, cap] int32 with ``hist_len`` / ``reply_from`` (the host
+    part of each row's token history and where its reply starts in it), ``rp`` / ``last_n`` /
+    ``pp`` / ``fp`` and the bias list ``bias_tok`` / ``bias_val`` [B, 300] with ``bias_n``. A decode
+    graph owns one and refills it per turn; the captured kernel reads these addresses."""
+
+    def __init__(self, batch: int, device, hist_cap: int = LOGIT_PROC_WINDOW, bias_cap: int = LOGIT_PROC_MAX_BIAS):
+        z = lambda *s, dt=torch.int32: torch.zeros(*s, dtype=dt, device=device)      # noqa: E731
+        self.hist, self.hist_len, self.reply_from = z(batch, max(1, hist_cap)), z(batch), z(batch)
+        self.rp = torch.ones(batch, dtype=torch.float32, device=device)
+        self.last_n = z(batch)
+        self.pp, self.fp = z(batch, dt=torch.float32), z(batch, dt=torch.float32)
+        self.bias_tok, self.bias_val = z(batch, max(1, bias_cap)), z(batch, max(1, bias_cap), dt=torch.float32)
+        self.bias_n = z(batch)
+        self.active = False
+
+    def fill(self, rows) -> "LogitProc":
+        """``rows``: per batch row ``(tokens, reply_start, params)`` — the row's whole host-side
+        history, the index in it where the reply starts, and an object with the SamplingParams
+        penalty fields — or None for a neutral (padding) row. Keeps the tail that fits ``hist``."""
+        B, cap = self.hist.shape
+        bcap = self.bias_tok.shape[1]
+        hist = torch.zeros(B, cap, dtype=torch.int32)
+        ints = torch.zeros(4, B, dtype=torch.int32)            # hist_len, reply_from, last_n, bias_n
+        flts = torch.zeros(3, B, dtype=torch.float32)          # rp, pp, fp
+        flts[0] = 1.0
+        btok = torch.zeros(B, bcap, dtype=torch.int32)
+        bval = torch.zeros(B, bcap, dtype=torch.float32)
+        self.active = False
+        for b, row in enumerate(rows):
+            if row is None or not row[2].has_processors():
+                continue
+            tokens, reply_start, p = row
+            self.active = True
+            keep = list(tokens[-cap:])
+            cut = len(tokens) - len(keep)
+            hist[b, :len(keep)] = torch.tensor(keep, dtype=torch.int32)
+            bias = list((p.logit_bias or {}).items())
+            if len(bias) > bcap:
+                raise ValueError(f"logit_bias has {len(bias)} entries; at most {bcap} are supported")
+            ints[:, b] = torch.tensor([len(keep), min(max(reply_start - cut, 0), len(keep)), p.repeat_last_n,
+                                       len(bias)], dtype=torch.int32)
+            flts[:, b] = torch.tensor([p.repetition_penalty, p.presence_penalty, p.frequency_penalty])
+            if bias:
+                btok[b, :len(bias)] = torch.tensor([int(t) for t, _ in bias], dtype=torch.int32)
+                bval[b, :len(bias)] = torch.tensor([float(v) for _, v in bias], dtype=torch.float32)
+        dev = self.hist.device
+        for dst, src in ((self.hist, hist), (self.hist_len, ints[0]), (self.reply_from, ints[1]),
+                         (self.last_n, ints[2]), (self.bias_n, ints[3]), (self.rp, flts[0]), (self.pp, flts[1]),
+                         (self.fp, flts[2]), (self.bias_tok, btok), (self.bias_val, bval)):
+            dst.copy_(src.to(dev, non_blocking=True))
+        return self
+
+
+def apply_logit_processors(logits: torch.Tensor, proc: LogitProc, out: Optional[torch.Tensor] = None,
+                           step: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """In place on ``logits`` [B, V] (bf16 or fp32, row stride >= V): logit_bias, then the repetition
+    penalty, then frequency / presence penalties, from each row's history
+    ``proc.hist[b, :hist_len[b]] ++ out[0:step, b]`` (csrc/logit_proc.hip; semantics:
+    ops/reference.py). ``step=None``: host history only. With the graph's ``out`` [steps, B] and
+    device ``step`` the call is capturable and reads the tokens K6 recorded in earlier replays."""
+    if _use_native(logits):
+        native().logit_proc(logits, proc.hist, proc.hist_len, proc.reply_from, proc.rp, proc.last_n, proc.pp, proc.fp,
+                            proc.bias_tok, proc.bias_val, proc.bias_n, out if step is not None else None, step)
+        return logits
+    return ref.apply_logit_processors(logits, proc, out, step)

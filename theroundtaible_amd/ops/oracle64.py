@@ -15,6 +15,11 @@ fp32 error (unit round-off 2^-24) that is far below a bf16 ulp except where term
 * ``gelu_tanh``: ``bf16_ulp(e) + 2^-21 * |x| + 2^-100``. ``1 + tanh`` carries about 2^-22
   absolute error, times 0.5 |x|, with 4x margin (it cancels for x in [-7, -4]).
 * RoPE: ``bf16_ulp(e) + 2^-20 * (|x1 c| + |x2 s|)``, the two products of the output at hand.
+* logit processors (csrc/logit_proc.hip; bf16 or fp32 logits): ``ulp(e) + 2^-22 * mag`` in the
+  storage dtype's ulp, with ``mag`` the largest magnitude any step of ``l + bias``, ``/ rp`` or ``* rp``,
+  ``- fp * c``, ``- pp`` reaches: the kernel rounds the product and each of the four steps to fp32,
+  five roundings of at most 2^-24 * mag each (a division by rp < 1 scales the error carried so
+  far by 1 / rp, and the step's magnitude with it), so 2^-22 * mag bounds their sum with 1.6x margin.
 
 The input builders of the CPU emulation test and the GPU test live here too, so both see the
 same bits.
@@ -44,17 +49,28 @@ def bf16_ulp(t: torch.Tensor) -> torch.Tensor:
     return torch.ldexp(torch.ones_like(a), ex - 8)
 
 
-def assert_within(got: torch.Tensor, e: torch.Tensor, tol: torch.Tensor, what: str = "") -> float:
-    """``|got - e| <= tol`` wherever ``e`` rounds to a finite bf16; NaN, +inf and -inf of ``got``
-    sit exactly where ``e`` rounded to bf16 has them. Returns the worst error / tolerance."""
-    assert got.dtype == torch.bfloat16, f"{what}: output is {got.dtype}, not bfloat16"
+def fp32_ulp(t: torch.Tensor) -> torch.Tensor:
+    """Spacing of fp32 at |t| (2^-16 of :func:`bf16_ulp`: 23 explicit mantissa bits against 7)."""
+    return bf16_ulp(t) * 2.0 ** -16
+
+
+def storage_ulp(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    return {torch.bfloat16: bf16_ulp, torch.float32: fp32_ulp}[dtype](t)
+
+
+def assert_within(got: torch.Tensor, e: torch.Tensor, tol: torch.Tensor, what: str = "",
+                  dtype: torch.dtype = torch.bfloat16) -> float:
+    """``|got - e| <= tol`` wherever ``e`` rounds to a finite bf16 (``dtype``: the storage type);
+    NaN, +inf and -inf of ``got`` sit exactly where ``e`` rounded to it has them. Returns the worst
+    error / tolerance."""
+    assert got.dtype == dtype, f"{what}: output is {got.dtype}, not {dtype}"
     g = got.detach().cpu().double().reshape(-1)
     e = e.double().reshape(-1)
     tol = tol.double().reshape(-1)
     assert g.shape == e.shape == tol.shape, f"{what}: shapes {tuple(g.shape)} {tuple(e.shape)} {tuple(tol.shape)}"
     if g.numel() == 0:
         return 0.0
-    eb = e.float().to(torch.bfloat16).double()
+    eb = e.float().to(dtype).double()
     for name, fn in (("NaN", torch.isnan), ("+inf", lambda v: v == float("inf")),
                      ("-inf", lambda v: v == float("-inf"))):
         bad = fn(g) != fn(eb)
@@ -145,6 +161,70 @@ def rope(x: torch.Tensor, cs: Optional[torch.Tensor]) -> Tuple[torch.Tensor, tor
 
 def rope_tol(e, mag):
     return bf16_ulp(e) + ROPE_SLACK * mag
+
+
+LOGIT_PROC_SLACK = 2.0 ** -22
+LOGIT_PROC_WINDOW = 2048
+LOGIT_PROC_MAX_BIAS = 300
+
+
+def apply_logit_processors(logits: torch.Tensor, proc, out=None, step=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fp64 twin of ops.apply_logit_processors, not in place: ``(e, mag, named)`` with ``e`` the
+    unrounded processed logits [B, V], ``mag`` the tolerance magnitude and ``named`` the mask of the
+    elements a history token or a bias entry names in a non-neutral row (every other element must
+    keep its bits). Written apart from ops/reference.py: whole-row bincounts, not a per-token loop."""
+    B, V = logits.shape
+    e = logits.detach().cpu().double().clone()
+    mag = e.abs()
+    mag = torch.where(torch.isfinite(mag), mag, torch.zeros_like(mag))
+    named = torch.zeros(B, V, dtype=torch.bool)
+    W = LOGIT_PROC_WINDOW
+    for b in range(B):
+        rp, pp, fp = (float(t[b]) for t in (proc.rp, proc.pp, proc.fp))
+        last_n = int(proc.last_n[b])
+        n_bias = min(max(int(proc.bias_n[b]), 0), proc.bias_tok.shape[1], LOGIT_PROC_MAX_BIAS)
+        rep_n = 0 if rp == 1.0 else (W if last_n < 0 else min(last_n, W))
+        if rep_n == 0 and pp == 0.0 and fp == 0.0 and n_bias == 0:
+            continue
+        n_host = min(max(int(proc.hist_len[b]), 0), proc.hist.shape[1])
+        S = proc.hist[b, :n_host].cpu().long()
+        if step is not None and out is not None:
+            S = torch.cat([S, out[:min(max(int(step.reshape(-1)[0]), 0), out.shape[0]), b].cpu().long()])
+        start = min(max(int(proc.reply_from[b]), 0), n_host)
+
+        def hits(part: torch.Tensor) -> torch.Tensor:
+            part = part[(part >= 0) & (part < V)]
+            return torch.bincount(part, minlength=V).double()
+
+        in_rep = hits(S[max(len(S) - rep_n, 0):]) > 0 if rep_n > 0 else torch.zeros(V, dtype=torch.bool)
+        reply = S[start:]
+        cnt = hits(reply[max(len(reply) - W, 0):]) if (pp != 0.0 or fp != 0.0) else torch.zeros(V, dtype=torch.float64)
+        bias = torch.zeros(V, dtype=torch.float64)
+        has_bias = torch.zeros(V, dtype=torch.bool)
+        for j in range(n_bias):                 # in order: a token named twice keeps its last entry
+            t = int(proc.bias_tok[b, j])
+            if 0 <= t < V:
+                bias[t] = float(proc.bias_val[b, j])
+                has_bias[t] = True
+        l = e[b]
+        live = l != float("-inf")
+        m = mag[b]
+        l1 = torch.where(has_bias & live, l + bias, l)
+        m = torch.maximum(m, torch.where(live, l1.abs(), m))
+        l2 = torch.where(in_rep & live, torch.where(l1 > 0, l1 / rp, l1 * rp), l1)
+        if rp > 0:      # dividing by rp < 1 scales the error carried so far by 1 / rp
+            m = torch.where(in_rep & live, torch.maximum(l2.abs(), m * max(1.0, 1.0 / rp)), m)
+        l3 = torch.where((cnt > 0) & live, l2 - fp * cnt, l2)
+        m = torch.maximum(m, torch.where(live, torch.maximum(l3.abs(), (fp * cnt).abs()), m))
+        l4 = torch.where((cnt > 0) & live, l3 - pp, l3)
+        m = torch.maximum(m, torch.where(live, l4.abs(), m))
+        e[b], mag[b] = l4, m
+        named[b] = has_bias | in_rep | (cnt > 0)
+    return e, mag, named
+
+
+def logit_proc_tol(e, mag, dtype: torch.dtype = torch.bfloat16):
+    return storage_ulp(e, dtype) + LOGIT_PROC_SLACK * mag
 
 
 # ---- input builders (shared by tests/test_elementwise_oracle_cpu.py and test_elementwise_gpu.py) --
@@ -281,3 +361,51 @@ def rope_case(hq: int, hkv: int, D: int, T: int, seed: int = 0, first_pos: int =
     kc = _randn((ROPE_BLOCKS, hkv, ROPE_BS, D), g)
     vc = _randn((ROPE_BLOCKS, hkv, D, ROPE_BS), g)
     return qkv, pos, slots, kc, vc
+
+
+# logit processors: B = 3 rows (neutral, penalties only, penalties + 300 biases)
+LOGIT_PROC_V = (32064, 1003)
+LOGIT_PROC_HIST = (0, 1, 2048, 3000)        # the last exceeds the window: truncated
+LOGIT_PROC_STEPS = (0, 1, 2500)
+LOGIT_PROC_OUT_ROWS = 2600
+LOGIT_PROC_HIST_CAP = 3008
+
+
+def logit_proc_case(V: int, dtype: torch.dtype, n_hist: int, step: int, seed: int = 0):
+    """-> (logits [3, V] of ``dtype``, proc (CPU ops.LogitProc), out [2600, 3] int64, step [1] int64).
+
+    History and bias tokens come from a pool ``{t, t + 4096, t + 8192}`` (one home slot of the
+    kernel's 4096-slot table each triple: probing) with duplicates and ids outside [0, V) mixed in;
+    the logits at pool tokens cycle through negative, zero, positive and -inf. Row 0 is neutral."""
+    from . import LogitProc
+    g = _gen(9000 + 13 * V + 7 * n_hist + step + 1000003 * seed + (dtype == torch.float32))
+    B = 3
+    base = torch.randperm(min(V, 4096), generator=g)[:96]
+    pool = torch.cat([base, base + 4096, base + 8192, torch.tensor([-1, -7, V, V + 7, 2 ** 31 - 1])])
+
+    def draw(n):
+        return pool[torch.randint(0, pool.numel(), (n,), generator=g)]
+
+    logits = (4.0 * torch.randn(B, V, generator=g)).to(dtype)
+    inside = pool[(pool >= 0) & (pool < V)]
+    vals = torch.tensor([-3.5, 0.0, 2.75, float("-inf"), -0.0, 7.0, -11.0, 0.40625]).to(dtype)
+    logits[:, inside] = vals[torch.arange(inside.numel()) % vals.numel()].expand(B, -1)
+    proc = LogitProc(B, "cpu", hist_cap=LOGIT_PROC_HIST_CAP)
+    for b in range(B):
+        proc.hist[b, :n_hist] = draw(n_hist).to(torch.int32)
+    proc.hist_len.fill_(n_hist)
+    proc.reply_from.copy_(torch.tensor([0, n_hist // 2, n_hist // 3], dtype=torch.int32))
+    k = (n_hist + step) % 4
+    proc.rp.copy_(torch.tensor([1.0, 1.3, 0.8]))
+    proc.last_n.copy_(torch.tensor([64, (64, -1, 0, 5000)[k], (-1, 1, 64, 2048)[k]], dtype=torch.int32))
+    proc.pp.copy_(torch.tensor([0.0, 0.4, -0.3]))
+    proc.fp.copy_(torch.tensor([0.0, 0.15, 0.07]))
+    nb = LOGIT_PROC_MAX_BIAS
+    n_in = min(100, inside.numel())             # the rest random: a token named twice keeps its last entry
+    proc.bias_tok[2, :nb] = torch.cat([inside[:n_in], torch.randperm(V, generator=g)[:nb - 2 - n_in],
+                                       torch.tensor([-1, V])]).to(torch.int32)
+    proc.bias_val[2, :nb] = (200.0 * torch.rand(nb, generator=g) - 100.0)
+    proc.bias_val[2, :4] = torch.tensor([-100.0, 100.0, 0.0, 1.5])
+    proc.bias_n[2] = nb
+    out = torch.stack([draw(LOGIT_PROC_OUT_ROWS) for _ in range(B)], dim=1).to(torch.int64).contiguous()
+    return logits, proc, out, torch.tensor([step], dtype=torch.int64)

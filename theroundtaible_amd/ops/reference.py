@@ -434,3 +434,62 @@ def paging_guard(block_tables, ctx_lens, positions, slots, err, num_blocks, bloc
                 if int(slots[b]) != want:
                     code |= 4
     err[0] = int(err[0]) | code
+
+
+# ---- logit processors (csrc/logit_proc.hip) -------------------------------------------------------
+
+LOGIT_PROC_WINDOW = 2048      # both windows (repetition set, counted reply) reach back this far
+LOGIT_PROC_MAX_BIAS = 300     # OpenAI's limit on logit_bias entries
+
+
+def logit_proc_history(proc, b: int, out=None, step=None) -> Tuple[list, int]:
+    """Row b's token history ``S = hist[b, :hist_len[b]] ++ out[0:step, b]`` (time order) and the
+    index in S at which the reply starts."""
+    n_host = min(max(int(proc.hist_len[b]), 0), proc.hist.shape[1])
+    S = [int(t) for t in proc.hist[b, :n_host].tolist()]
+    if step is not None and out is not None:
+        n_dev = min(max(int(step.reshape(-1)[0]), 0), out.shape[0])
+        S += [int(t) for t in out[:n_dev, b].tolist()]
+    return S, min(max(int(proc.reply_from[b]), 0), n_host)
+
+
+def apply_logit_processors(logits: torch.Tensor, proc, out=None, step=None) -> torch.Tensor:
+    """Semantics of csrc/logit_proc.hip (in place, fp32 on the stored logit, one rounding on the
+    store): bias, then the repetition penalty over the last ``last_n`` tokens of S, then frequency
+    and presence over the reply part of S; both windows capped at LOGIT_PROC_WINDOW. Tokens
+    outside [0, V) are ignored, -inf stays -inf, unnamed elements and neutral rows are not touched."""
+    B, V = logits.shape
+    f32 = lambda v: torch.tensor(float(v), dtype=torch.float32)       # noqa: E731
+    for b in range(B):
+        rp, pp, fp = f32(proc.rp[b]), f32(proc.pp[b]), f32(proc.fp[b])
+        nb = min(max(int(proc.bias_n[b]), 0), proc.bias_tok.shape[1], LOGIT_PROC_MAX_BIAS)
+        ln = int(proc.last_n[b])
+        n_rep = 0 if (float(rp) == 1.0 or ln == 0) else (LOGIT_PROC_WINDOW if ln < 0 else min(ln, LOGIT_PROC_WINDOW))
+        counted = float(pp) != 0.0 or float(fp) != 0.0
+        if n_rep == 0 and not counted and nb == 0:
+            continue
+        S, rf = logit_proc_history(proc, b, out, step)
+        bias = {}
+        for j in range(nb):                      # a token named twice: the last entry holds
+            bias[int(proc.bias_tok[b, j])] = f32(proc.bias_val[b, j])
+        rep = set(S[len(S) - min(n_rep, len(S)):])
+        count: dict = {}
+        if counted:
+            for t in S[rf:][-LOGIT_PROC_WINDOW:]:
+                count[t] = count.get(t, 0) + 1
+        for t in set(bias) | rep | set(count):
+            if not 0 <= t < V:
+                continue
+            l = logits[b, t].float()
+            if float(l) == float("-inf"):
+                continue
+            if t in bias:
+                l = l + bias[t]
+            if t in rep:
+                l = l / rp if float(l) > 0 else l * rp
+            c = count.get(t, 0)
+            if c > 0:
+                l = l - fp * f32(c)
+                l = l - pp
+            logits[b, t] = l.to(logits.dtype)
+    return logits

@@ -633,7 +633,11 @@ class RoundtableServer:
                 opts = body.get("options") or {}
                 params = {"temperature": opts.get("temperature"), "top_p": opts.get("top_p"),
                           "top_k": opts.get("top_k"), "seed": opts.get("seed"),
-                          "max_tokens": opts.get("num_predict"), "stop": opts.get("stop")}
+                          "max_tokens": opts.get("num_predict"), "stop": opts.get("stop"),
+                          # Ollama's names; absent = neutral (Ollama's own 1.1 default is NOT adopted)
+                          "repetition_penalty": opts.get("repeat_penalty"), "repeat_last_n": opts.get("repeat_last_n"),
+                          "presence_penalty": opts.get("presence_penalty"),
+                          "frequency_penalty": opts.get("frequency_penalty")}
                 if body.get("stream"):
                     # Ollama's NDJSON stream: one message object per line, then a done record
                     # (a request without "stream" keeps the one-object reply of rounds 1-5)
@@ -691,10 +695,24 @@ class RoundtableServer:
             max_tokens = num("max_completion_tokens", self.default_max_tokens, int)
         if max_tokens < 1:
             raise ValueError("max_tokens must be >= 1")
-        return SamplingParams(temperature=num("temperature", 0.7, float), top_p=num("top_p", 1.0, float),
-                              top_k=num("top_k", 0, int), seed=num("seed", 0, int),
-                              max_new_tokens=min(max_tokens, 8192), ignore_eos=bool(body.get("ignore_eos", False)),
-                              stop_on_consensus=False)
+        bias = body.get("logit_bias")
+        if bias is not None:
+            if not isinstance(bias, dict):
+                raise ValueError("'logit_bias' must be an object of token id -> bias")
+            try:    # OpenAI sends the token ids as strings
+                bias = {int(k): float(v) for k, v in bias.items()}
+            except (TypeError, ValueError):
+                raise ValueError("'logit_bias' keys must be token ids and its values numbers") from None
+        params = SamplingParams(temperature=num("temperature", 0.7, float), top_p=num("top_p", 1.0, float),
+                                top_k=num("top_k", 0, int), seed=num("seed", 0, int),
+                                max_new_tokens=min(max_tokens, 8192), ignore_eos=bool(body.get("ignore_eos", False)),
+                                stop_on_consensus=False,
+                                repetition_penalty=num("repetition_penalty", 1.0, float),
+                                repeat_last_n=num("repeat_last_n", 64, int),
+                                presence_penalty=num("presence_penalty", 0.0, float),
+                                frequency_penalty=num("frequency_penalty", 0.0, float), logit_bias=bias or None)
+        params.check_processors(int(self.engine.cfg.vocab))      # ValueError -> HTTP 400
+        return params
 
     def submit(self, prompt, body: Dict[str, Any], session: Optional[str], stream: bool = False) -> _Request:
         params = self.sampling(body)
