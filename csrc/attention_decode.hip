@@ -1,20 +1,19 @@
 // K3: paged-KV decode attention (one query token per sequence), GQA, MFMA bf16, split-KV.
-// The work-item code is in attn_core.h (shared with the persistent decode-layer kernel); this
-// file holds the grid launch: blockIdx = (sequence x kv head, key split).
-#include "attn_core.h"
+// What lives where:
+//   attn_core.h  the device core (shared with the persistent decode-layer experiment): the work
+//                item attn_item, and the rules with one copy each — item_range (an item's keys),
+//                group_record (a row's effective group), merge_state (two softmax states);
+//   attn_plan.h  the pure host plan: knobs, grids, kernel variant, which combine runs and its
+//                geometry (combine_slot_bound), tested without a GPU by csrc/tests/host_check.cpp;
+//   this file    the three kernels around the core — attention (blockIdx = (sequence x kv head,
+//                key split)), the per-step work plan, the separate split combine — and the
+//                launchers: validate -> plan -> fill AttnArgs -> dispatch.
+#include "attn_plan.h"
 
-#include <cstdlib>
+#include <type_traits>
 
 namespace {
 using namespace attn;
-
-// XCD-aware item order (p.xcd): blocks are dealt round-robin over the 8 XCDs (block b runs on
-// the XCD of b % 8, the same class->XCD map in consecutive launches: tools/probes/xcc_probe.hip),
-// so item j = (lin % 8) * (nwg / 8) + lin / 8 gives each XCD a contiguous run of items. Items are
-// ordered kv head slowest: one kv head's (sequence, split) items, whose partials its rows'
-// combine reads, share an XCD — and decode_combine_kernel orders its rows the same way. A
-// different placement changes only speed.
-RT_DEVICE int xcd_item(int lin, int nwg) { return (lin & 7) * (nwg >> 3) + (lin >> 3); }
 
 // the LDS-DMA staged form (LM_GLDS) puts each wave's K/V slice over the merge buffers
 template <int D, int GM, int W, int LM>
@@ -27,17 +26,7 @@ template <int D, int GM, int W = NW, bool PP = true, int LM = 0>
 __global__ void __launch_bounds__(W * 64) paged_decode_kernel(AttnArgs p) {
   static_assert(sizeof(DecodeSmem<D, GM, W, LM>) <= 160 * 1024, "LDS of one CU");
   __shared__ DecodeSmem<D, GM, W, LM> sm_;
-  auto& sm = sm_.m;
-  int bh = blockIdx.x, split = blockIdx.y;
-  if (p.xcd) {
-    const int ns = gridDim.y, nb = gridDim.x / p.Hkv;
-    const int j = xcd_item(blockIdx.x + gridDim.x * blockIdx.y, gridDim.x * ns);
-    const int hk = j / (nb * ns), rem = j - hk * (nb * ns);
-    const int b = rem / ns;
-    split = rem - b * ns;
-    bh = b * p.Hkv + hk;
-  }
-  attn_item<D, false, GM, W, PP, LM>(p, bh, split, sm);
+  attn_item<D, false, GM, W, PP, LM>(p, blockIdx.x, blockIdx.y, sm_.m);
 }
 
 // Per-step work plan: one workgroup per item (sequence b, split) writes the item's key range
@@ -77,26 +66,14 @@ __global__ void __launch_bounds__(256) attn_plan_kernel(AttnArgs p, int G, int G
 template <int D, int SPL>
 __global__ void __launch_bounds__(1024) decode_combine_kernel(AttnArgs p) {
   const int G = p.Hq / p.Hkv;
-  int row = blockIdx.x;                        // b * Hq + query head
-  int chunk = blockIdx.y;
-  if (p.xcd) {   // rows of one kv head on the XCD that ran its attention items (xcd_item)
-    const int nc = gridDim.y, nb = gridDim.x / p.Hq;
-    const int j = xcd_item(blockIdx.x + gridDim.x * blockIdx.y, gridDim.x * nc);
-    const int per_h = nb * G * nc;
-    const int hk = j / per_h, r1 = j - hk * per_h;
-    const int bb = r1 / (G * nc), r2 = r1 - bb * (G * nc);
-    const int hh = r2 / nc;
-    chunk = r2 - hh * nc;
-    row = bb * p.Hq + hk * G + hh;
-  }
+  const int row = blockIdx.x;                  // b * Hq + query head
+  const int chunk = blockIdx.y;
   const int b = row / p.Hq;
   const int dl = threadIdx.x & 7, sl = threadIdx.x >> 3;
   const int nsl = blockDim.x >> 3;
   const int d0 = chunk * 32 + 4 * dl;
   const int stride = p.slot_stride > 0 ? p.slot_stride : p.num_splits;
-  // the host's sizing: every split of every member of the largest group (slots past the row's
-  // own count are inside the row's stride and loaded, never merged)
-  const int nmax = p.groups != nullptr ? min(stride, (16 / G) * p.num_splits) : p.num_splits;
+  const int nmax = combine_slot_bound(p.groups != nullptr, G, p.num_splits, stride);   // the host's sizing
   const float* __restrict__ po = p.part_o + (size_t)row * stride * D;
   const float* __restrict__ pml = p.part_ml + (size_t)row * stride * 4;
   // the group record and the first chunk's partials are independent: both requests go out
@@ -115,24 +92,13 @@ __global__ void __launch_bounds__(1024) decode_combine_kernel(AttnArgs p) {
     nn = p.groups[3 * b + 1];
     sh = p.groups[3 * b + 2];
   }
-  int n = 1;
-  if (p.groups != nullptr && !(nn < 1 || nn * G > 16 || b0 < 0 || b < b0 || b - b0 >= nn || sh < 0))
-    n = nn;                                    // as attn_item
-  const int nslots = n * p.num_splits;
+  const int nslots = group_record(p.groups != nullptr, b0, nn, sh, b, G).n * p.num_splits;
   if (nslots == 1) return;                     // written directly by the attention launch
   float M = -INFINITY, L = 0.f;
   float4_ O = {0.f, 0.f, 0.f, 0.f};
-  auto merge = [&](float m2, float l2, float4_ o2) {
-    if (!(l2 > 0.f)) return;
-    const float Mc = fmaxf(M, m2);
-    const float a = M == -INFINITY ? 0.f : exp2f(M - Mc), f = exp2f(m2 - Mc);
-    O = O * a + f * o2;
-    L = L * a + f * l2;
-    M = Mc;
-  };
 #pragma unroll
   for (int j = 0; j < SPL; ++j)
-    if (sl + j * nsl < nslots) merge(mlv[j][0], mlv[j][1], ov[j]);
+    if (sl + j * nsl < nslots) merge_state(M, L, O, mlv[j][0], mlv[j][1], ov[j]);
   // more chunks only for rows with more slots than the host sized for (not reached when the
   // group record is well-formed: n * G <= 16)
   for (int base = SPL * nsl; base < nslots; base += SPL * nsl) {
@@ -144,7 +110,7 @@ __global__ void __launch_bounds__(1024) decode_combine_kernel(AttnArgs p) {
     }
 #pragma unroll
     for (int j = 0; j < SPL; ++j)
-      if (base + sl + j * nsl < nslots) merge(mlv[j][0], mlv[j][1], ov[j]);
+      if (base + sl + j * nsl < nslots) merge_state(M, L, O, mlv[j][0], mlv[j][1], ov[j]);
   }
   // the 8 slot-lanes of a wave (lane bits 3..5), then the waves through LDS; fixed order
   auto xmerge = [&](int x, bool upper) {
@@ -156,9 +122,9 @@ __global__ void __launch_bounds__(1024) decode_combine_kernel(AttnArgs p) {
       const float mm = M, ll = L;
       const float4_ oo = O;
       M = m2; L = l2; O = o2;
-      merge(mm, ll, oo);
+      merge_state(M, L, O, mm, ll, oo);
     } else {
-      merge(m2, l2, o2);
+      merge_state(M, L, O, m2, l2, o2);
     }
   };
 #pragma unroll
@@ -177,11 +143,11 @@ __global__ void __launch_bounds__(1024) decode_combine_kernel(AttnArgs p) {
     M = -INFINITY; L = 0.f; O = float4_{0.f, 0.f, 0.f, 0.f};
     if (w < nwaves) {
       const float* e = red[w][dl];
-      merge(e[4], e[5], float4_{e[0], e[1], e[2], e[3]});
+      merge_state(M, L, O, e[4], e[5], float4_{e[0], e[1], e[2], e[3]});
     }
     if (w + 8 < nwaves) {
       const float* e = red[w + 8][dl];
-      merge(e[4], e[5], float4_{e[0], e[1], e[2], e[3]});
+      merge_state(M, L, O, e[4], e[5], float4_{e[0], e[1], e[2], e[3]});
     }
 #pragma unroll
     for (int x = 8; x < 64; x <<= 1) xmerge(x, w & (x >> 3));
@@ -191,128 +157,67 @@ __global__ void __launch_bounds__(1024) decode_combine_kernel(AttnArgs p) {
     }
   }
 }
+
+// Runtime value -> compile-time constant: f(integral_constant<int, V>) for the V that equals v;
+// -2 if none does (the plan has refused such values before a dispatch sees them).
+template <int... Vs, class F>
+int with_const(int v, F&& f) {
+  int rc = -2;
+  ((v == Vs ? void(rc = f(std::integral_constant<int, Vs>{})) : void()), ...);
+  return rc;
+}
+
+int launch(void (*kernel)(AttnArgs), dim3 grid, dim3 block, hipStream_t stream, const AttnArgs& args) {
+  hipLaunchKernelGGL(kernel, grid, block, 0, stream, args);
+  return hipGetLastError() == hipSuccess ? 0 : -6;
+}
 }  // namespace
 
+// The limits the Python side repeats (ops/__init__.py), exported so a test holds them together
+int attn_plan_hdr() { return PLAN_HDR; }
+int attn_max_splits() { return MAXS; }
+int attn_group_cols() { return GROUP_COLS; }
 
 // q [B, Hq, D]; k_cache [NB, Hkv, 32, D] (chunk-major blocks, common.h kc_elem); v_cache [NB, Hkv, D, 32]; block_tables [B, max_blocks] int32;
 // defer_combine: leave the separate combine to the caller (*deferred = 1 when it was needed);
 // part_o >= B*Hq*slot_stride*D floats, part_ml >= B*Hq*slot_stride*4 floats, counters >= B*Hkv ints
 // (zeroed once). groups: nullptr or [B][3] {first, n, shared blocks} (shared-prefix groups,
 // attn_core.h); slot_stride >= max n * num_splits (0 = num_splits, no groups).
+// Returns 0, the plan's refusal (attn_plan.h AttnPlan::rc: -1 .. -5) or -6: a launch failed.
 int launch_paged_decode(void* out, const void* q, const void* k_cache, const void* v_cache, const int* block_tables,
                         const int* ctx_lens, float* part_o, float* part_ml, int* counters, int B, int Hq, int Hkv,
                         int D, int max_blocks, float scale, int num_splits, const int* groups, int slot_stride,
                         hipStream_t stream, int defer_combine, int* deferred, const int* plan, int plan_stride) {
   if (deferred != nullptr) *deferred = 0;
-  if (B == 0) return 0;
-  if (Hq % Hkv || Hq / Hkv > 16) return -1;
-  if (num_splits < 1) num_splits = 1;
-  if (num_splits > MAXS) return -3;
-  dim3 grid(B * Hkv, num_splits), block(NW * 64);
-  const float sl2 = scale * LOG2E;
-  if (groups != nullptr && slot_stride < num_splits) return -4;
+  const AttnKnobs& kn = knobs();
+  const AttnPlan pl = plan_paged_decode(B, Hq, Hkv, D, num_splits, groups != nullptr, slot_stride, plan != nullptr,
+                                        plan_stride, defer_combine != 0, kn);
+  if (pl.rc != 0 || pl.gx == 0) return pl.rc;
   AttnArgs args{(uint16_t*)out, (const uint16_t*)q, (const uint16_t*)k_cache, (const uint16_t*)v_cache,
-                      block_tables, ctx_lens, part_o, part_ml, counters, Hq, Hkv, max_blocks, sl2, num_splits,
-                      groups, groups != nullptr ? slot_stride : 0};
-  static const int probe = getenv("RT_ATTN_PROBE") ? atoi(getenv("RT_ATTN_PROBE")) : 0;
-  args.probe = probe;
-  if (plan != nullptr) {
-    if (plan_stride <= PLAN_HDR) return -5;
-    args.plan = plan;
-    args.plan_stride = plan_stride;
-  }
-  // separate combine launch from this many splits on (RT_ATTN_EXT_SPLITS pins it; 0 = never):
-  // r03 probes, 3 knights x 40K shared keys: in-launch combine 8.7 us at 16 splits (48 slots),
-  // 23 us at 64 (192 slots); whole launch(es), grouped B=3: tp8 shard 32.6 -> 14.9 us (64
-  // splits), tp1 41.0 -> 38.7 us (8 splits) — the extra boundary costs less than the serial
-  // combine on one CU at every measured split count (profiles/r03/attn_ext_combine.md)
-  static const int ext_min = getenv("RT_ATTN_EXT_SPLITS") ? atoi(getenv("RT_ATTN_EXT_SPLITS")) : 2;
-  args.ext_combine = (ext_min > 0 && num_splits >= ext_min && probe == 0) ? 1 : 0;
-  // A/B knobs (profiles/r05/attn_xcd_ab.md): XCD-aware item order in both launches, and plain
-  // (L2-resident) partial stores for the separate combine
-  static const int xcd_env = getenv("RT_ATTN_XCD") ? atoi(getenv("RT_ATTN_XCD")) : 0;
-  // latency decomposition only (microbench): the attention launch without its combine launch
-  static const bool skip_combine = getenv("RT_ATTN_SKIP_COMBINE") && atoi(getenv("RT_ATTN_SKIP_COMBINE")) == 1;
-  static const int plain_env = getenv("RT_ATTN_PLAIN_PARTIALS") ? atoi(getenv("RT_ATTN_PLAIN_PARTIALS")) : 0;
-  const bool hk_split_ok = Hkv % 8 == 0 || 8 % Hkv == 0;
-  args.xcd = (xcd_env && (B * Hkv * num_splits) % 8 == 0 && (B * Hq * (D / 32)) % 8 == 0 && hk_split_ok) ? 1 : 0;
-  args.plain_partials = (plain_env && args.ext_combine && !defer_combine) ? 1 : 0;
-  const int G = Hq / Hkv;
-  // a group's n*G columns need the 16-column LDS merge buffers
-  // K/V loop form (attn_core.h PP): the copy-free ping-pong wins where a workgroup streams many
-  // tiles (Llama-3-8B tp 1, 8 KV heads: 3 knights x 22K shared keys 29.6 -> 28.7 us, 40K 41.1 ->
-  // 40.8 us) and loses ~0.3 us on the short ranges of 1-2 KV-head shards (tp 4 / 8), which keep the
-  // copy loop (profiles/r05/attn_pingpong_ab.md). RT_ATTN_PP=0 / 1 pins it (A/B).
-  static const int pp_env = getenv("RT_ATTN_PP") ? atoi(getenv("RT_ATTN_PP")) : -1;
-  const bool pp = pp_env >= 0 ? pp_env != 0 : Hkv >= 4;
-  // K/V load mode (attn_core.h LM_*): nontemporal K and V loads. With the chunk-major K blocks,
-  // tp 1, 3 knights x 22K / 40K shared keys 27.6 -> 25.4 / 41.9 -> 37.8 us; rows with distinct
-  // contexts B = 1 25K 25.9 -> 23.7, B = 3 25K 59.3 -> 55.3, B = 16 2K 31.0 -> 28.6; tp 8 shard even
-  // (profiles/r06/attn_kchunk.md). The one loser: ungrouped rows that read the SAME blocks (3 rows
-  // over one 22K prefix without groups, 33.5 -> 35.4: the 2nd / 3rd reads no longer hit L2 / MALL)
-  // — the engine decodes shared prefixes as groups, so that case does not arise there.
-  // RT_ATTN_LM pins the mode (0 = default policy, 1 = K nt, 2 = V nt, 3 = both; A/B; 7 = both
-  // through the LDS-DMA staged loop, ping-pong form only).
-  static const int lm_env = getenv("RT_ATTN_LM") ? atoi(getenv("RT_ATTN_LM")) : (LM_NTK | LM_NTV);
-  const int lm = (lm_env & LM_GLDS) && pp ? 7 : lm_env & 3;
-  args.lm = lm;
-#define RT_PD3(DV, PPV, LMV)                                                                                          \
-  do {                                                                                                                \
-    if (groups != nullptr) hipLaunchKernelGGL((paged_decode_kernel<DV, 16, NW, PPV, LMV>), grid, block, 0, stream, args); \
-    else if (G <= 4) hipLaunchKernelGGL((paged_decode_kernel<DV, 4, NW, PPV, LMV>), grid, block, 0, stream, args);   \
-    else if (G <= 8) hipLaunchKernelGGL((paged_decode_kernel<DV, 8, NW, PPV, LMV>), grid, block, 0, stream, args);   \
-    else hipLaunchKernelGGL((paged_decode_kernel<DV, 16, NW, PPV, LMV>), grid, block, 0, stream, args);              \
-  } while (0)
-#define RT_PD2(DV, PPV)                             \
-  do {                                              \
-    if (lm == 0) RT_PD3(DV, PPV, 0);                \
-    else if (lm == 1) RT_PD3(DV, PPV, 1);           \
-    else if (lm == 2) RT_PD3(DV, PPV, 2);           \
-    else if (lm == 3 || !PPV) RT_PD3(DV, PPV, 3);   \
-    else RT_PD3(DV, PPV, 7);                        \
-  } while (0)
-#define RT_PD(DV) do { if (pp) RT_PD2(DV, true); else RT_PD2(DV, false); } while (0)
-  // (16-wave grouped workgroups were measured and rejected: __launch_bounds__(1024) caps the item
-  // at 128 VGPRs, it spills, and half the CUs stream — 22K shared keys 25.0 -> 41.6 us at 6 splits,
-  // profiles/r06/attn_kchunk.md)
-  if (D == 128) RT_PD(128);
-  else if (D == 64) RT_PD(64);
-  else return -2;
-#undef RT_PD
-#undef RT_PD2
-#undef RT_PD3
-  if (args.ext_combine && defer_combine && D == 128) {
-    // the caller runs the combine inside the next launch (combine_o.hip: combine + o-projection)
-    if (deferred != nullptr) *deferred = 1;
-  } else if (args.ext_combine && !skip_combine) {
-    // slots per row: every split of every member of the largest group (groups: n * G <= 16)
-    const int nmax = groups != nullptr ? min(slot_stride, (16 / G) * num_splits) : num_splits;
-    // slot-lanes (x 8 dim-lanes) per workgroup, capped at 32 (RT_COMBINE_NSL): fewer, wider lanes
-    // (8 slots each for a tp 8 table's 256-slot bound) beat 128 lanes x 2 — 4 waves to dispatch
-    // and merge instead of 16; tp 8 grouped attention + combine 12.4 -> 11.6 us
-    // (profiles/r04/combine_lanes_ab.md)
-    static const int nsl_cap = [] {
-      const char* e = getenv("RT_COMBINE_NSL");
-      const int v = e ? atoi(e) : 32;
-      return (v >= 8 && v <= 128 && v % 8 == 0) ? v : 32;
-    }();
-    int nsl = min(nsl_cap, (nmax + 7) / 8 * 8);
-    int spl = (nmax + nsl - 1) / nsl;                       // slots per lane per chunk
-    spl = spl <= 1 ? 1 : (spl <= 2 ? 2 : (spl <= 4 ? 4 : 8));
-    if ((nmax + spl - 1) / spl < nsl) nsl = ((nmax + spl - 1) / spl + 7) / 8 * 8;
-    const dim3 cgrid(B * Hq, D / 32), cblock(8 * nsl);
-#define RT_CB(DV)                                                                                   \
-  do {                                                                                              \
-    if (spl <= 1) hipLaunchKernelGGL((decode_combine_kernel<DV, 1>), cgrid, cblock, 0, stream, args); \
-    else if (spl <= 2) hipLaunchKernelGGL((decode_combine_kernel<DV, 2>), cgrid, cblock, 0, stream, args); \
-    else if (spl <= 4) hipLaunchKernelGGL((decode_combine_kernel<DV, 4>), cgrid, cblock, 0, stream, args); \
-    else hipLaunchKernelGGL((decode_combine_kernel<DV, 8>), cgrid, cblock, 0, stream, args);          \
-  } while (0)
-    if (D == 128) RT_CB(128);
-    else RT_CB(64);
-#undef RT_CB
-  }
-  return 0;
+                block_tables, ctx_lens, part_o, part_ml, counters, Hq, Hkv, max_blocks, scale * LOG2E, pl.splits,
+                groups, groups != nullptr ? slot_stride : 0};
+  args.probe = kn.probe;
+  args.ext_combine = pl.ext_combine ? 1 : 0;
+  args.plan = plan;
+  args.plan_stride = plan != nullptr ? plan_stride : 0;
+  int rc = with_const<128, 64>(D, [&](auto d) {
+    return with_const<4, 8, 16>(pl.GM, [&](auto gm) {
+      return with_const<1, 0>(pl.pp, [&](auto pp) {
+        return with_const<0, 1, 2, 3, 7>(pl.lm, [&](auto lm) {
+          return launch(paged_decode_kernel<d(), gm(), NW, pp() != 0, lm()>, dim3(pl.gx, pl.gy), dim3(pl.block),
+                        stream, args);
+        });
+      });
+    });
+  });
+  if (rc != 0) return rc;
+  if (pl.deferred && deferred != nullptr) *deferred = 1;
+  if (!pl.combine) return 0;
+  return with_const<128, 64>(D, [&](auto d) {
+    return with_const<1, 2, 4, 8>(pl.spl, [&](auto spl) {
+      return launch(decode_combine_kernel<d(), spl()>, dim3(pl.cgx, pl.cgy), dim3(pl.cblock), stream, args);
+    });
+  });
 }
 
 // The per-step plan for launch_paged_decode's ``plan`` (same B, heads, num_splits, groups, block
@@ -320,7 +225,7 @@ int launch_paged_decode(void* out, const void* q, const void* k_cache, const voi
 int launch_attn_plan(int* plan, int plan_stride, const int* block_tables, const int* ctx_lens, const int* groups,
                      int B, int Hq, int Hkv, int max_blocks, int num_splits, hipStream_t stream) {
   if (B == 0) return 0;
-  if (Hq % Hkv || Hq / Hkv > 16 || num_splits < 1 || num_splits > MAXS || plan_stride <= PLAN_HDR) return -1;
+  if (Hq % Hkv || Hq / Hkv > GROUP_COLS || num_splits < 1 || num_splits > MAXS || plan_stride <= PLAN_HDR) return -1;
   AttnArgs args{};
   args.block_tables = block_tables;
   args.ctx_lens = ctx_lens;
@@ -328,6 +233,6 @@ int launch_attn_plan(int* plan, int plan_stride, const int* block_tables, const 
   args.num_splits = num_splits;
   args.groups = groups;
   args.plan_stride = plan_stride;
-  hipLaunchKernelGGL(attn_plan_kernel, dim3(B, num_splits), dim3(256), 0, stream, args, Hq / Hkv, 16, plan);
+  hipLaunchKernelGGL(attn_plan_kernel, dim3(B, num_splits), dim3(256), 0, stream, args, Hq / Hkv, GROUP_COLS, plan);
   return hipGetLastError() == hipSuccess ? 0 : -4;
 }

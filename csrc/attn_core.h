@@ -41,6 +41,7 @@ using rt::short8;
 constexpr int BS = 32;
 constexpr int NW = 8;
 constexpr int MAXS = 64;  // max splits per (sequence, kv head)
+constexpr int GROUP_COLS = 16;  // MFMA columns a shared-prefix group's query heads may fill (n * G)
 constexpr float LOG2E = 1.4426950408889634f;
 
 template <int D>
@@ -125,9 +126,6 @@ struct AttnArgs {
   int slot_stride = 0;         // partial slots per (sequence, head) >= n * num_splits; 0 = num_splits
   int probe = 0;               // latency probe (microbench only, RT_ATTN_PROBE): stop after phase k
   int ext_combine = 0;         // 1: leave every partial for decode_combine_kernel (no in-launch combine)
-  int xcd = 0;                 // 1: XCD-aware item order (attention_decode.hip), the launch's grid % 8 == 0
-  int plain_partials = 0;      // 1 (ext_combine only): partials stay in the writer's L2 (plain stores)
-  int lm = 0;                  // K/V load mode actually launched (LM_*), for the host's record
   // per-step work plan (attn_plan_kernel; nullptr = derive it in every launch): per item
   // (sequence, split), PLAN_HDR header ints then the item's block ids, plan_stride ints per item
   const int* plan = nullptr;
@@ -143,14 +141,25 @@ struct ItemRange {
   int b0, n, sh, ctx, sh_b, nsh, pr_b, nv;
 };
 
-RT_DEVICE ItemRange item_range(int ctx, int g0, int g1, int g2, bool grouped, int b, int split, int G, int GM,
-                               int num_splits) {
+// The effective group of sequence b from its record {g0 = first sequence, g1 = size, g2 = shared
+// blocks}: no record or a malformed one -> the row runs alone. The ONE copy of this rule: the
+// attention items, the plan and both combines (decode_combine_kernel, tools/experiments/
+// combine_o.hip) must agree on n, or a combine merges slots nobody wrote. `cols` is the column
+// count the caller's LDS holds; every launch with groups runs GM == GROUP_COLS
+// (attn_plan.h), so attn_item's g1 * G > GM and the combines' g1 * G > GROUP_COLS are one test.
+struct GroupRec {
+  int b0, n, sh;
+};
+RT_HD GroupRec group_record(bool grouped, int g0, int g1, int g2, int b, int G, int cols = GROUP_COLS) {
+  const bool bad = !grouped | (g1 < 1) | (g1 * G > cols) | (g0 < 0) | (b < g0) | (b - g0 >= g1) | (g2 < 0);
+  return GroupRec{bad ? b : g0, bad ? 1 : g1, bad ? 0 : g2};
+}
+
+RT_HD ItemRange item_range(int ctx, int g0, int g1, int g2, bool grouped, int b, int split, int G, int GM,
+                           int num_splits) {
   ItemRange it;
-  const bool bad = !grouped | (g1 < 1) | (g1 * G > GM) | (g0 < 0) | (b < g0) | (b - g0 >= g1) | (g2 < 0);
-  it.b0 = bad ? b : g0;   // no / malformed group record: run alone
-  it.n = bad ? 1 : g1;
-  it.sh = bad ? 0 : g2;
-  it.ctx = ctx;
+  const GroupRec gr = group_record(grouped, g0, g1, g2, b, G, GM);
+  it.b0 = gr.b0, it.n = gr.n, it.sh = gr.sh, it.ctx = ctx;
   const int mi = b - it.b0, nslots = it.n * num_splits, slot = mi * num_splits + split;
   const int ntiles = (ctx + BS - 1) / BS;
   // this workgroup's shared chunk (all members' columns) then its private split (own columns)
@@ -176,6 +185,19 @@ struct AttnSmem {
   int s_last;                  // bit m: this workgroup combines member m
 };
 
+// Merge the softmax state (m2, l2, o2) into (M, L, O): m = running max (log2 domain), l = sum of
+// 2^(s - m), O = the unnormalised output. A state with no live key (l2 == 0) is skipped; the
+// empty state is (-inf, 0, 0). Every split combine merges through this one function, in an
+// order fixed by its caller.
+RT_HD void merge_state(float& M, float& L, float4_& O, float m2, float l2, float4_ o2) {
+  if (!(l2 > 0.f)) return;
+  const float Mc = fmaxf(M, m2);
+  const float a = M == -INFINITY ? 0.f : exp2f(M - Mc), f = exp2f(m2 - Mc);
+  O = O * a + f * o2;
+  L = L * a + f * l2;
+  M = Mc;
+}
+
 RT_DEVICE void store_bf16x4(uint16_t* dst, float a, float b_, float c, float d, bool sc1) {
   uint2 pk;
   pk.x = rt::pack2(a, b_);
@@ -189,8 +211,7 @@ RT_DEVICE void store_bf16x4(uint16_t* dst, float a, float b_, float c, float d, 
 
 // One (sequence, kv head, key split) work item. Returns true when this workgroup wrote final
 // output rows (no split, or the last-arriving split that combined them).
-// W = waves per workgroup (8; 16 for grouped launches: twice the K/V in flight per CU and
-// enough threads to combine a whole group's slots in one round trip).
+// W = waves per workgroup (8: 16 were measured and rejected, attn_plan.h).
 // PP: ping-pong K/V tiles (two in flight per wave); false = the round-4 cur/nxt copy loop (A/B)
 // LM: K/V load mode (LM_NTK / LM_NTV above)
 template <int D, bool SC1, int GM = 16, int W = NW, bool PP = true, int LM = 0>
@@ -498,19 +519,10 @@ RT_DEVICE bool attn_item(const AttnArgs& P, int bh, int split, AttnSmem<D, GM, W
     if (nslots == 1) {
       const float inv = L > 0.f ? 1.f / L : 0.f;
       store_bf16x4(out + (q0 + row) * D + d0, O[0] * inv, O[1] * inv, O[2] * inv, O[3] * inv, SC1);
-    } else {
-      if (P.plain_partials) {
-        // read by the NEXT launch only (decode_combine_kernel): the kernel boundary orders them,
-        // and plain stores keep the lines in this XCD's L2, where an XCD-aware combine reads them
-        const size_t e = ((q0 + row) * stride + slot);
-        *reinterpret_cast<float4_*>(part_o + e * D + d0) = O;
-        if (d0 == 0) *reinterpret_cast<float4_*>(part_ml + e * 4) = float4_{M, L, 0.f, 0.f};
-      } else {
-        // partials leave as 16-B write-through (sc1) stores: the combining workgroup, possibly
-        // on another XCD, reads them with sc1 loads and no L2 writeback/invalidate is needed
-        rt::sc1_store4(po_rsrc, ((row * stride + slot) * D + d0) * 4, O);
-        if (d0 == 0) rt::sc1_store4(pml_rsrc, (row * stride + slot) * 16, float4_{M, L, 0.f, 0.f});
-      }
+    } else {   // partials leave as 16-B write-through (sc1) stores: the combining workgroup, possibly
+      // on another XCD, reads them with sc1 loads and no L2 writeback/invalidate is needed
+      rt::sc1_store4(po_rsrc, ((row * stride + slot) * D + d0) * 4, O);
+      if (d0 == 0) rt::sc1_store4(pml_rsrc, (row * stride + slot) * 16, float4_{M, L, 0.f, 0.f});
     }
   }
   if (nslots == 1) {
@@ -619,13 +631,10 @@ RT_DEVICE bool attn_item(const AttnArgs& P, int bh, int split, AttnSmem<D, GM, W
     if (grp == 0) {
       for (int q2 = 1; q2 < Q; ++q2) {
         const float* e = scr + ((q2 - 1) * nitems + it) * 6;
-        const float Me = e[4];
-        if (Me == -INFINITY || e[5] <= 0.f) continue;
-        const float Mc = fmaxf(Mr, Me);
-        const float a = Mr == -INFINITY ? 0.f : exp2f(Mr - Mc), f = exp2f(Me - Mc);
-        O = O * a + f * float4_{e[0], e[1], e[2], e[3]};
-        Lr = Lr * a + f * e[5];
-        Mr = Mc;
+        // a group's state has l > 0 only with a finite m (the online softmax; the chunk merge
+        // above adds only slots with l > 0), so merge_state's skip test !(l > 0) skips exactly the
+        // states this merge always skipped (m == -inf or l <= 0)
+        merge_state(Mr, Lr, O, e[4], e[5], float4_{e[0], e[1], e[2], e[3]});
       }
     }
   }

@@ -21,6 +21,9 @@ int launch_paged_decode(void* out, const void* q, const void* k_cache, const voi
                         hipStream_t stream, int defer_combine, int* deferred, const int* plan, int plan_stride);
 int launch_attn_plan(int* plan, int plan_stride, const int* block_tables, const int* ctx_lens, const int* groups,
                      int B, int Hq, int Hkv, int max_blocks, int num_splits, hipStream_t stream);
+int attn_plan_hdr();     // attn_core.h PLAN_HDR, MAXS, GROUP_COLS
+int attn_max_splits();
+int attn_group_cols();
 int prefill_rows_per_tile(int G, int D);
 int launch_prefill_split(void* out, const void* q, const void* k_cache, const void* v_cache, const int* block_tables,
                          const int* cu_q, const int* start_pos, const int* items, int n_items, const int* cmap,
@@ -216,7 +219,7 @@ int64_t paged_attention_decode(torch::Tensor out, torch::Tensor q, torch::Tensor
   const int* pp = nullptr;
   if (plan.has_value() && plan->defined()) {
     check_type(*plan, torch::kInt32, "plan");
-    TORCH_CHECK(plan_stride > 8 && plan->numel() >= B * num_splits * plan_stride, "attention plan too small");
+    TORCH_CHECK(plan_stride > attn_plan_hdr() && plan->numel() >= B * num_splits * plan_stride, "attention plan too small");
     pp = plan->data_ptr<int>();
   }
   int deferred = 0;
@@ -237,7 +240,7 @@ void attn_plan(torch::Tensor plan, int64_t plan_stride, torch::Tensor block_tabl
   check_type(block_tables, torch::kInt32, "block_tables");
   check_type(ctx_lens, torch::kInt32, "ctx_lens");
   TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) >= B && ctx_lens.numel() >= B, "metadata shape");
-  TORCH_CHECK(plan_stride > 8 && plan.numel() >= B * num_splits * plan_stride, "attention plan too small");
+  TORCH_CHECK(plan_stride > attn_plan_hdr() && plan.numel() >= B * num_splits * plan_stride, "attention plan too small");
   const int* gp = nullptr;
   if (groups.has_value() && groups->defined()) {
     check_type(*groups, torch::kInt32, "groups");
@@ -913,4 +916,8 @@ PYBIND11_MODULE(_C, m) {
         py::arg("rp"), py::arg("last_n"), py::arg("pp"), py::arg("fp"), py::arg("bias_tok"), py::arg("bias_val"),
         py::arg("bias_n"), py::arg("out") = py::none(), py::arg("step") = py::none());
   m.attr("arch") = "gfx950";
+  // the attention limits ops/__init__.py repeats for its CPU path (tests hold the two together)
+  m.attr("ATTN_PLAN_HDR") = attn_plan_hdr();
+  m.attr("ATTN_MAX_SPLITS") = attn_max_splits();
+  m.attr("ATTN_GROUP_COLS") = attn_group_cols();
 }

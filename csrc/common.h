@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #define RT_DEVICE __device__ __forceinline__
+#define RT_HD __host__ __device__ __forceinline__   // rules the host tests run too
 
 namespace rt {
 

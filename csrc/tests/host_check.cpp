@@ -1,13 +1,17 @@
-// Host-side argument validation of the HIP launchers, built with AddressSanitizer +
-// UndefinedBehaviorSanitizer on the HOST code only (GPU ASan / xnack+ is not
-// available on the MI355X pool). Every case below must be rejected BEFORE any HIP call, so
-// the binary runs on a machine without a GPU. Build + run: tests/test_native_host_sanitizers.py.
+// Host-side argument validation of the HIP launchers and the pure host rules behind them (the
+// launch plans of skinny_plan.h / attn_plan.h, the weight-layout map, the attention item ranges),
+// built with AddressSanitizer + UndefinedBehaviorSanitizer on the HOST code only (SURVEY §5.2;
+// GPU ASan / xnack+ is not available on the MI355X pool). Every launcher case below must be
+// rejected BEFORE any HIP call, so the binary runs on a machine without a GPU.
+// Build + run: tests/test_native_host_sanitizers.py.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <vector>
 
+#include "attn_plan.h"
 #include "skinny_plan.h"
 
 int launch_skinny_gemm(void* out, const void* x, const void* Ws, void* res, int M, int N, int K, int ldo, float eps,
@@ -169,7 +173,208 @@ static void check_plans() {
   EXPECT(resolve_order(4, 256, false, false, 99) == 0);
 }
 
+// plan of a decode attention launch, default knobs unless given
+static attn::AttnPlan aplan(int B, int Hq, int Hkv, int D, int splits, bool grouped, int stride,
+                            const attn::AttnKnobs& kn = attn::AttnKnobs{}, bool defer = false, bool has_plan = false,
+                            int plan_stride = 0) {
+  return attn::plan_paged_decode(B, Hq, Hkv, D, splits, grouped, stride, has_plan, plan_stride, defer, kn);
+}
+static bool attn_is(const attn::AttnPlan& p, int gx, int gy, int GM, bool pp, int lm) {
+  return p.rc == 0 && p.gx == gx && p.gy == gy && p.splits == gy && p.block == 512 && p.GM == GM && p.pp == pp &&
+         p.lm == lm;
+}
+static bool combine_is(const attn::AttnPlan& p, int nmax, int nsl, int spl, int cgx, int cgy) {
+  return p.rc == 0 && p.ext_combine && !p.deferred && p.combine && p.nmax == nmax && p.nsl == nsl && p.spl == spl &&
+         p.cblock == 8 * nsl && p.cgx == cgx && p.cgy == cgy;
+}
+static bool no_combine(const attn::AttnPlan& p, bool ext, bool deferred) {
+  return p.rc == 0 && p.ext_combine == ext && p.deferred == deferred && !p.combine;
+}
+
+// Expected values worked out by hand from the launcher's rules as they stood before the plan existed.
+static void check_attn_plans() {
+  using namespace attn;
+  // the table (Llama-3-8B tp 1, 3 knights): 4 members x 10 splits = 40 slots -> 2 per lane on 24 lanes
+  const AttnPlan t = aplan(3, 32, 8, 128, 10, true, 40);
+  EXPECT(attn_is(t, 24, 10, 16, true, 3) && combine_is(t, 40, 24, 2, 96, 4));
+  // its tp 8 shard: one kv head keeps the copy loop; 256 slots -> 8 per lane on 32 lanes
+  const AttnPlan s8 = aplan(3, 4, 1, 128, 64, true, 256);
+  EXPECT(attn_is(s8, 3, 64, 16, false, 3) && combine_is(s8, 256, 32, 8, 12, 4));
+  const AttnPlan u = aplan(6, 32, 8, 128, 8, false, 0);
+  EXPECT(attn_is(u, 48, 8, 4, true, 3) && combine_is(u, 8, 8, 1, 192, 4));
+  EXPECT(no_combine(aplan(6, 32, 8, 128, 1, false, 0), false, false));   // one split: written by the launch
+  EXPECT(no_combine(aplan(3, 32, 8, 128, 1, true, 4), false, false));    // grouped, one split: in-launch combine
+  // GM: 16 with groups, else by G
+  EXPECT(aplan(2, 12, 12, 64, 3, false, 0).GM == 4 && aplan(2, 32, 8, 128, 3, false, 0).GM == 4);
+  EXPECT(aplan(2, 20, 4, 128, 3, false, 0).GM == 8 && aplan(2, 28, 4, 128, 3, false, 0).GM == 8);
+  EXPECT(aplan(2, 64, 8, 128, 3, false, 0).GM == 8 && aplan(2, 36, 4, 128, 3, false, 0).GM == 16);
+  EXPECT(aplan(2, 64, 4, 128, 3, false, 0).GM == 16 && aplan(2, 12, 12, 64, 3, true, 48).GM == 16);
+  // D = 64: two 32-dim chunks per combined row
+  const AttnPlan d64 = aplan(2, 12, 12, 64, 3, false, 0);
+  EXPECT(attn_is(d64, 24, 3, 4, true, 3) && combine_is(d64, 3, 8, 1, 24, 2));
+  // return codes, each ahead of every later one: empty batch, head ratio, (splits < 1 clamped,)
+  // splits > MAXS, group slots < splits, plan row without ids, head dim
+  const AttnPlan e = aplan(0, 30, 8, 100, 65, true, 2, AttnKnobs{}, false, true, 8);
+  EXPECT(e.rc == 0 && e.gx == 0 && !e.combine && !e.deferred);
+  EXPECT(aplan(2, 30, 8, 100, 65, true, 2, AttnKnobs{}, false, true, 8).rc == -1);
+  EXPECT(aplan(2, 64, 2, 100, 65, true, 2, AttnKnobs{}, false, true, 8).rc == -1);   // G = 32 > 16
+  EXPECT(attn_is(aplan(2, 32, 8, 128, 0, false, 0), 16, 1, 4, true, 3));
+  EXPECT(attn_is(aplan(2, 32, 8, 128, -5, true, 1), 16, 1, 16, true, 3));
+  EXPECT(aplan(2, 32, 8, 100, 65, true, 2, AttnKnobs{}, false, true, 8).rc == -3);
+  EXPECT(aplan(2, 32, 8, 128, 64, false, 0).rc == 0);
+  EXPECT(aplan(2, 32, 8, 100, 4, true, 2, AttnKnobs{}, false, true, 8).rc == -4);
+  EXPECT(aplan(2, 32, 8, 100, 4, false, 2, AttnKnobs{}, false, false, 8).rc == -2);   // stride, plan stride unused
+  EXPECT(aplan(2, 32, 8, 100, 4, true, 4, AttnKnobs{}, false, true, 8).rc == -5);
+  EXPECT(aplan(2, 32, 8, 100, 4, true, 4, AttnKnobs{}, false, true, 9).rc == -2);
+  EXPECT(aplan(2, 32, 8, 128, 4, true, 4, AttnKnobs{}, false, true, 9).rc == 0);
+  EXPECT(aplan(2, 32, 8, 96, 4, false, 0).rc == -2 && aplan(2, 32, 8, 256, 4, false, 0).rc == -2);
+  // defer_combine: the caller combines D = 128 rows; D = 64 keeps the combine launch
+  EXPECT(no_combine(aplan(3, 32, 8, 128, 10, true, 40, AttnKnobs{}, true), true, true));
+  EXPECT(combine_is(aplan(2, 12, 12, 64, 3, false, 0, AttnKnobs{}, true), 3, 8, 1, 24, 2));
+  EXPECT(no_combine(aplan(3, 32, 8, 128, 1, true, 4, AttnKnobs{}, true), false, false));
+  // every knob still steers the plan
+  AttnKnobs k;
+  k.ext_splits = 0;
+  EXPECT(no_combine(aplan(3, 32, 8, 128, 10, true, 40, k), false, false));
+  EXPECT(no_combine(aplan(3, 32, 8, 128, 10, true, 40, k, true), false, false));
+  k = AttnKnobs{}, k.ext_splits = 4;
+  EXPECT(no_combine(aplan(6, 32, 8, 128, 3, false, 0, k), false, false));
+  EXPECT(combine_is(aplan(6, 32, 8, 128, 4, false, 0, k), 4, 8, 1, 192, 4));
+  k = AttnKnobs{}, k.pp = 0;
+  EXPECT(attn_is(aplan(3, 32, 8, 128, 10, true, 40, k), 24, 10, 16, false, 3));
+  k = AttnKnobs{}, k.pp = 1;
+  EXPECT(attn_is(aplan(3, 4, 1, 128, 64, true, 256, k), 3, 64, 16, true, 3));
+  EXPECT(aplan(2, 16, 4, 128, 3, false, 0).pp && !aplan(2, 6, 3, 128, 3, false, 0).pp);   // the rule: Hkv >= 4
+  for (int lm = 0; lm <= 3; ++lm) {
+    k = AttnKnobs{}, k.lm = lm;
+    EXPECT(aplan(3, 32, 8, 128, 10, true, 40, k).lm == lm && aplan(3, 4, 1, 128, 64, true, 256, k).lm == lm);
+  }
+  k = AttnKnobs{}, k.lm = 7;   // the staged loop exists in the ping-pong form only
+  EXPECT(aplan(3, 32, 8, 128, 10, true, 40, k).lm == 7 && aplan(3, 4, 1, 128, 64, true, 256, k).lm == 3);
+  k.pp = 0;
+  EXPECT(aplan(3, 32, 8, 128, 10, true, 40, k).lm == 3);
+  k.pp = 1;
+  EXPECT(aplan(3, 4, 1, 128, 64, true, 256, k).lm == 7);
+  k = AttnKnobs{}, k.lm = 5;
+  EXPECT(aplan(3, 32, 8, 128, 10, true, 40, k).lm == 7 && aplan(3, 4, 1, 128, 64, true, 256, k).lm == 1);
+  k = AttnKnobs{}, k.skip_combine = true;
+  EXPECT(no_combine(aplan(3, 32, 8, 128, 10, true, 40, k), true, false));
+  EXPECT(no_combine(aplan(3, 32, 8, 128, 10, true, 40, k, true), true, true));
+  k = AttnKnobs{}, k.probe = 2;   // a probe times the in-launch form
+  EXPECT(no_combine(aplan(3, 32, 8, 128, 10, true, 40, k), false, false));
+  k = AttnKnobs{}, k.combine_nsl = 16;
+  EXPECT(combine_is(aplan(3, 32, 8, 128, 10, true, 40, k), 40, 16, 4, 96, 4));
+  EXPECT(combine_is(aplan(3, 4, 1, 128, 64, true, 256, k), 256, 16, 8, 12, 4));   // 128 of 256 slots per chunk
+  k = AttnKnobs{}, k.combine_nsl = 128;
+  EXPECT(combine_is(aplan(3, 32, 8, 128, 10, true, 40, k), 40, 40, 1, 96, 4));
+  EXPECT(combine_is(aplan(3, 4, 1, 128, 64, true, 256, k), 256, 128, 2, 12, 4));
+  for (const int bad : {0, 4, 20, 136, -8}) {
+    k = AttnKnobs{}, k.combine_nsl = bad;
+    EXPECT(combine_is(aplan(3, 32, 8, 128, 10, true, 40, k), 40, 24, 2, 96, 4));
+  }
+  // the slot bound the kernel shares with the plan
+  EXPECT(combine_slot_bound(true, 4, 10, 40) == 40 && combine_slot_bound(true, 4, 10, 30) == 30);
+  EXPECT(combine_slot_bound(true, 7, 3, 100) == 6 && combine_slot_bound(false, 4, 10, 40) == 10);
+  EXPECT(combine_slot_bound(false, 4, 10, 0) == 10 && combine_slot_bound(true, 16, 5, 5) == 5);
+}
+
+// the combine launch's geometry against what decode_combine_kernel assumes of it
+static void check_combine_geometry() {
+  for (const int G : {1, 2, 4, 7, 8, 16})
+    for (const int splits : {2, 3, 10, 33, 64})
+      for (int grouped = 0; grouped <= 1; ++grouped)
+        for (int cap = 8; cap <= 128; cap += 8) {
+          attn::AttnKnobs k;
+          k.combine_nsl = cap;
+          const int stride = grouped ? (16 / G) * splits : 0;
+          const attn::AttnPlan p = aplan(2, G, 1, 128, splits, grouped != 0, stride, k);
+          const bool ok = p.rc == 0 && p.combine && p.nmax == (grouped ? stride : splits) && p.cblock == 8 * p.nsl &&
+                          p.nsl % 8 == 0 && p.nsl >= 8 && p.nsl <= cap && p.cblock <= 1024 &&
+                          (p.spl == 1 || p.spl == 2 || p.spl == 4 || p.spl == 8) &&
+                          (p.nsl * p.spl >= p.nmax || (p.spl == 8 && p.nsl == cap));   // else: the extra-chunk loop
+          EXPECT(ok);
+          if (!ok) std::fprintf(stderr, "  G %d splits %d grouped %d cap %d\n", G, splits, grouped, cap);
+        }
+}
+
+// The items of sequence b (record {first, n, sh}, `ctx` keys) over `splits`: private ranges cover
+// [it.sh, ceil(ctx / 32)) exactly once and nothing below; shared chunks are counted into `shared`.
+static bool private_cover(int ctx, int first, int n, int sh, bool grouped, int b, int G, int splits,
+                          const attn::GroupRec& want, std::vector<int>* shared) {
+  const int ntiles = (ctx + 31) / 32;
+  std::vector<int> seen(ntiles, 0);
+  for (int split = 0; split < splits; ++split) {
+    const attn::ItemRange it = attn::item_range(ctx, first, n, sh, grouped, b, split, G, 16, splits);
+    if (it.b0 != want.b0 || it.n != want.n || it.sh != want.sh || it.ctx != ctx) return false;
+    const int npr = it.nv - it.nsh;   // nv = shared chunk + private tiles
+    if (it.nsh < 0 || it.sh_b < 0 || it.sh_b + it.nsh > it.sh || npr < 0 || it.pr_b < it.sh ||
+        (npr > 0 && it.pr_b + npr > ntiles))
+      return false;
+    if (it.nsh > 0 && shared == nullptr) return false;
+    for (int t = 0; t < it.nsh; ++t) ++(*shared)[it.sh_b + t];
+    for (int t = 0; t < npr; ++t) ++seen[it.pr_b + t];
+  }
+  for (int t = 0; t < ntiles; ++t)
+    if (seen[t] != (t >= want.sh ? 1 : 0)) return false;
+  return true;
+}
+
+// item_range partitions a group's keys: no gap (keys dropped), no overlap (keys counted twice)
+static void check_item_range() {
+  const std::vector<std::vector<int>> tail_sets = {{1}, {33}, {0, 1, 500}, {31, 32, 33, 2000}};
+  int cases = 0;
+  for (const int G : {1, 4, 8, 16})
+    for (int n = 1; n <= 16 / G; ++n)
+      for (const int splits : {1, 2, 3, 8, 10, 64})
+        for (const int sh : {0, 1, 2, 7, 59, 64, 1250})
+          for (const auto& tails : tail_sets)
+            for (const int first : {0, 2}) {
+              std::vector<int> shared(sh, 0);
+              bool ok = true;
+              for (int i = 0; i < n && ok; ++i) {
+                int ctx = sh * 32 + tails[i % tails.size()];
+                if (ctx < 1) ctx = 1;
+                ok = private_cover(ctx, first, n, sh, true, first + i, G, splits, attn::GroupRec{first, n, sh}, &shared);
+              }
+              for (int t = 0; t < sh; ++t) ok = ok && shared[t] == 1;   // over all n * splits items
+              EXPECT(ok);
+              if (!ok) std::fprintf(stderr, "  G %d n %d splits %d sh %d first %d\n", G, n, splits, sh, first);
+              ++cases;
+            }
+  EXPECT(cases == 7728);
+  // no record, or a malformed one: the row runs alone over all of its keys
+  const int G = 4, b = 3;
+  const int bad[][3] = {{2, 0, 5}, {2, -1, 5}, {0, 5, 5}, {-1, 4, 5}, {4, 2, 5}, {0, 3, 5}, {1, 2, 5}, {2, 2, -1}};
+  for (const auto& r : bad)
+    for (const int ctx : {1, 32, 33, 5000})
+      for (const int splits : {1, 3, 64})
+        EXPECT(private_cover(ctx, r[0], r[1], r[2], true, b, G, splits, attn::GroupRec{b, 1, 0}, nullptr));
+  EXPECT(private_cover(777, 2, 2, 5, false, b, G, 10, attn::GroupRec{b, 1, 0}, nullptr));
+  const attn::GroupRec good = attn::group_record(true, 2, 2, 5, b, G);
+  EXPECT(good.b0 == 2 && good.n == 2 && good.sh == 5);
+  EXPECT(attn::group_record(true, 2, 2, 5, b, G, 4).n == 1);   // LDS for 4 columns only: alone
+}
+
+static void check_merge_state() {
+  using rt::float4_;
+  const auto same = [](float4_ a, float4_ b) { return a[0] == b[0] && a[1] == b[1] && a[2] == b[2] && a[3] == b[3]; };
+  const float4_ o2 = {1.f, -2.f, 3.5f, 0.f};
+  float M = -INFINITY, L = 0.f;
+  float4_ O = {0.f, 0.f, 0.f, 0.f};
+  attn::merge_state(M, L, O, 1.5f, 2.f, o2);   // into the empty state: the other state's values
+  EXPECT(M == 1.5f && L == 2.f && same(O, o2));
+  attn::merge_state(M, L, O, 100.f, 0.f, float4_{9.f, 9.f, 9.f, 9.f});   // a partner without keys is skipped
+  attn::merge_state(M, L, O, -INFINITY, 0.f, float4_{0.f, 0.f, 0.f, 0.f});
+  EXPECT(M == 1.5f && L == 2.f && same(O, o2));
+  attn::merge_state(M, L, O, 2.5f, 1.f, float4_{1.f, 1.f, 1.f, 1.f});    // the larger max rescales the state by 1/2
+  EXPECT(M == 2.5f && L == 2.f && same(O, float4_{1.5f, 0.f, 2.75f, 1.f}));
+}
+
 int main() {
+  check_attn_plans();
+  check_combine_geometry();
+  check_item_range();
+  check_merge_state();
   // decode GEMM: M outside [1, 32] (17..32 only with plain / norm prologues and no all-reduce), K not a
   // multiple of 32, N not a multiple of 16, missing operands
   EXPECT(launch_skinny_gemm(nullptr, nullptr, nullptr, nullptr, 0, 16, 64, 16, 1e-5f, 0, 0, nullptr, nullptr,

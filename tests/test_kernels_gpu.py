@@ -25,6 +25,10 @@ def close(a, b, atol, rtol=0.0):
 def test_native_loaded():
     assert ops.native_available()
     assert ops.native().arch == "gfx950"
+    # the attention limits ops repeats for its CPU path are the kernels' own
+    assert ops.PLAN_HDR == ops.native().ATTN_PLAN_HDR and ops.PLAN_STRIDE > ops.PLAN_HDR
+    assert ops.MAX_SPLITS == ops.native().ATTN_MAX_SPLITS
+    assert ops.MAX_GROUP_COLS == ops.native().ATTN_GROUP_COLS
 
 
 @pytest.mark.parametrize("H", [256, 768, 4096, 8192])

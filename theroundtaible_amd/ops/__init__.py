@@ -95,12 +95,17 @@ def rope_and_cache(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: Optional
     return ref.rope_and_cache(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, n_heads, n_kv_heads, head_dim)
 
 
+# Limits of the decode attention kernels, repeated from csrc/attn_core.h (GROUP_COLS, MAXS, PLAN_HDR)
+# because the CPU path imports without the native module, which exports them as ATTN_GROUP_COLS,
+# ATTN_MAX_SPLITS and ATTN_PLAN_HDR (tests/test_kernels_gpu.py holds the two together).
 MAX_GROUP_COLS = 16      # MFMA columns a shared-prefix group's query heads may fill (n * G)
+MAX_SPLITS = 64          # key splits per (sequence, kv head)
+PLAN_HDR = 8             # header ints of an attention plan row
 
 
-# attention plan row: 8 header ints + 512 block ids (the 8 waves x 64 lanes of an item's first
+# attention plan row: the header ints + 512 block ids (the 8 waves x 64 lanes of an item's first
 # block-id fetch; an item with more tiles reads the rest from the block tables)
-PLAN_STRIDE = 8 + 512
+PLAN_STRIDE = PLAN_HDR + 512
 
 
 def plan_enabled() -> bool:
@@ -149,7 +154,7 @@ def device_cus(device=None) -> int:
     return _CUS[idx]
 
 
-def decode_splits(batch: int, n_kv_heads: int, num_cus: Optional[int] = None, max_splits: int = 64,
+def decode_splits(batch: int, n_kv_heads: int, num_cus: Optional[int] = None, max_splits: int = MAX_SPLITS,
                   grouped: bool = False) -> int:
     """Split-KV count fixed per (batch bucket, kv heads): at most one 8-wave workgroup per CU
     (measured on MI355X, profiles/r01_microbench_v1.log: B=3, ctx 6000 -> 8 splits 22 µs,

@@ -28,6 +28,7 @@
 namespace {
 using namespace skinny;
 using attn::AttnArgs;
+using attn::merge_state;
 
 constexpr long long BAR_POLL_LIMIT = 1ll << 24;
 
@@ -41,15 +42,6 @@ struct CombineArgs {
   int* err;
 };
 
-RT_DEVICE void merge_state(float& M, float& L, float4_& O, float m2, float l2, float4_ o2) {
-  if (!(l2 > 0.f)) return;
-  const float Mc = fmaxf(M, m2);
-  const float a = M == -INFINITY ? 0.f : exp2f(M - Mc), f = exp2f(m2 - Mc);
-  O = O * a + f * o2;
-  L = L * a + f * l2;
-  M = Mc;
-}
-
 // one (row = b * Hq + head, 32-dim chunk) unit on the 128 threads `t` of a half workgroup
 template <int D>
 RT_DEVICE void combine_unit(const CombineArgs& c, int unit, bool live, int t, int half, float (*red)[2][8][6]) {
@@ -62,7 +54,7 @@ RT_DEVICE void combine_unit(const CombineArgs& c, int unit, bool live, int t, in
   int n = 1;
   if (c.groups != nullptr) {
     const int b0 = c.groups[3 * b], nn = c.groups[3 * b + 1], sh = c.groups[3 * b + 2];
-    if (!(nn < 1 || nn * G > 16 || b0 < 0 || b < b0 || b - b0 >= nn || sh < 0)) n = nn;   // as attn_item
+    n = attn::group_record(true, b0, nn, sh, b, G).n;
   }
   const int nslots = n * c.num_splits;
   float M = -INFINITY, L = 0.f;

@@ -166,7 +166,7 @@ int launch_decode_layer(void* res, void* q, void* a, void* g, const void* wqkv, 
                         float* part_ml, int* split_counters, int* sync, int* err, long long* stamps, int M, int H,
                         int I, int Hq, int Hkv, int head_dim, int BS, int max_blocks, int num_splits, float eps,
                         float scale, hipStream_t stream) {
-  if (head_dim != D || M < 1 || M > 16 || H % 32 || I % 32 || Hq % Hkv || Hq / Hkv > 16 || BS != 32) return -1;
+  if (head_dim != D || M < 1 || M > 16 || H % 32 || I % 32 || Hq % Hkv || Hq / Hkv > attn::GROUP_COLS || BS != attn::BS) return -1;
   if (num_splits < 1 || num_splits > attn::MAXS) return -2;
   const int grid = decode_layer_grid();
   if (grid <= 0) return -3;
@@ -184,7 +184,7 @@ int launch_decode_layer(void* res, void* q, void* a, void* g, const void* wqkv, 
                   nullptr};
   P.at = attn::AttnArgs{(uint16_t*)a, (const uint16_t*)q, (const uint16_t*)k_cache, (const uint16_t*)v_cache,
                         block_tables, ctx_lens, part_o, part_ml, split_counters, Hq, Hkv, max_blocks,
-                        scale * 1.4426950408889634f, num_splits};
+                        scale * attn::LOG2E, num_splits};
   P.n_qkv = Nqkv / 16;
   P.n_o = H / 16;
   P.n_gu = I / 16;
