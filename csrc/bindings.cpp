@@ -8,6 +8,8 @@
 
 #include <vector>
 
+#include "logprobs_plan.h"
+
 void launch_norm(void* out, const void* x, void* res, const void* w, const void* b, int rows, int H, float eps,
                  bool add, bool ln, hipStream_t stream);
 void launch_rope_cache(void* q_out, const void* qkv, const int64_t* positions, const float* cos_sin, void* k_cache,
@@ -66,6 +68,10 @@ int launch_logit_proc(void* logits, int dtype, int B, int V, int64_t ld, const i
                       const int* hist_len, const int* reply_from, const float* rp, const int* last_n, const float* pp,
                       const float* fp, const int* bias_tok, const float* bias_val, const int* bias_n, int bias_cap,
                       const int64_t* out, const int64_t* step, int max_steps, int out_ld, hipStream_t stream);
+int launch_token_logprobs(const void* logits, int dtype, int B, int V, int64_t ld, const int* n_top, float* ws,
+                          int64_t ws_words, const int64_t* ids, const int64_t* out, const int64_t* step,
+                          int max_steps, int out_ld, float* tok_lp, int* top_id, float* top_lp, int rec_steps,
+                          int rec_ld, int rec_cols, hipStream_t stream);
 int oneshot_create(int world, int rank, int cap_elems, char* handles);
 int oneshot_open(int id, const char* all_handles);
 int oneshot_capacity(int id);
@@ -717,6 +723,60 @@ void logit_proc(torch::Tensor logits, torch::Tensor hist, torch::Tensor hist_len
   TORCH_CHECK(rc == 0, "logit_proc: unsupported configuration (rc=", rc, ")");
 }
 
+// Logprobs (csrc/logprobs.hip): the chosen token's log-probability and the n_top[b] most likely tokens of
+// logits [B, V] (row stride >= V), read only, into record row 0 (ids [B]) or, with the graph's out
+// [steps, B] and device step, into record row *step - 1 for the token out[*step - 1, b]; capturable.
+void token_logprobs(torch::Tensor logits, torch::Tensor n_top, torch::Tensor ws, torch::Tensor tok_lp,
+                    torch::Tensor top_id, torch::Tensor top_lp, c10::optional<torch::Tensor> ids,
+                    c10::optional<torch::Tensor> out, c10::optional<torch::Tensor> step) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1,
+              "token_logprobs: logits must be [B, V] rows");
+  const auto st = logits.scalar_type();
+  TORCH_CHECK(st == torch::kBFloat16 || st == torch::kFloat32, "token_logprobs: logits must be bfloat16 or float32");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  const int64_t ld = B > 1 ? logits.stride(0) : V;
+  TORCH_CHECK(ld >= V && V < (int64_t(1) << 31), "token_logprobs: row stride must be >= V");
+  check_type(n_top, torch::kInt32, "n_top");
+  check_type(ws, torch::kFloat32, "ws");
+  check_type(tok_lp, torch::kFloat32, "tok_lp");
+  check_type(top_id, torch::kInt32, "top_id");
+  check_type(top_lp, torch::kFloat32, "top_lp");
+  TORCH_CHECK(tok_lp.dim() == 2 && top_id.dim() == 3 && top_lp.sizes() == top_id.sizes() &&
+                  top_id.size(0) == tok_lp.size(0) && top_id.size(1) == tok_lp.size(1),
+              "token_logprobs: records tok_lp [steps, B], top_id / top_lp [steps, B, n]");
+  TORCH_CHECK(n_top.numel() >= B && tok_lp.size(1) >= B, "token_logprobs: per-row tensors must cover the batch");
+  const bool has_out = out.has_value() && out->defined(), has_step = step.has_value() && step->defined();
+  const bool has_ids = ids.has_value() && ids->defined();
+  TORCH_CHECK(has_out == has_step, "token_logprobs: out and step go together");
+  TORCH_CHECK(has_out != has_ids, "token_logprobs: either ids or (out, step)");
+  const int64_t* ip = nullptr;
+  const int64_t* op = nullptr;
+  const int64_t* sp = nullptr;
+  int max_steps = 0, out_ld = 0;
+  if (has_out) {
+    check_type(*out, torch::kInt64, "out");
+    check_type(*step, torch::kInt64, "step");
+    TORCH_CHECK(out->dim() == 2 && step->numel() >= 1, "token_logprobs: out [steps, B], step [1]");
+    TORCH_CHECK(out->size(1) >= B, "token_logprobs: out must cover the batch");
+    TORCH_CHECK(tok_lp.size(0) >= out->size(0), "token_logprobs: records must cover the steps of out");
+    op = out->data_ptr<int64_t>();
+    sp = step->data_ptr<int64_t>();
+    max_steps = (int)out->size(0);
+    out_ld = (int)out->size(1);
+  } else {
+    check_type(*ids, torch::kInt64, "ids");
+    TORCH_CHECK(ids->numel() >= B, "token_logprobs: ids must cover the batch");
+    ip = ids->data_ptr<int64_t>();
+  }
+  const int rc = launch_token_logprobs(logits.data_ptr(), st == torch::kBFloat16 ? 0 : 1, (int)B, (int)V, ld,
+                                       n_top.data_ptr<int>(), ws.data_ptr<float>(), ws.numel(), ip, op, sp, max_steps,
+                                       out_ld, tok_lp.data_ptr<float>(), top_id.data_ptr<int>(),
+                                       top_lp.data_ptr<float>(), (int)tok_lp.size(0), (int)tok_lp.size(1),
+                                       (int)top_id.size(2), cur_stream());
+  TORCH_CHECK(rc == 0, "token_logprobs: unsupported configuration (rc=", rc, ")");
+}
+int64_t logprobs_workspace_floats(int64_t B) { return lpr::workspace_words((int)B); }
+
 void shuffle_weight(torch::Tensor Ws, torch::Tensor W, c10::optional<torch::Tensor> gamma, int64_t rope_heads,
                     int64_t head_dim, bool swiglu) {
   check_bf16(Ws, "Ws");
@@ -915,6 +975,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("logit_proc", &logit_proc, py::arg("logits"), py::arg("hist"), py::arg("hist_len"), py::arg("reply_from"),
         py::arg("rp"), py::arg("last_n"), py::arg("pp"), py::arg("fp"), py::arg("bias_tok"), py::arg("bias_val"),
         py::arg("bias_n"), py::arg("out") = py::none(), py::arg("step") = py::none());
+  m.def("token_logprobs", &token_logprobs, py::arg("logits"), py::arg("n_top"), py::arg("ws"), py::arg("tok_lp"),
+        py::arg("top_id"), py::arg("top_lp"), py::arg("ids") = py::none(), py::arg("out") = py::none(),
+        py::arg("step") = py::none());
+  m.def("logprobs_workspace_floats", &logprobs_workspace_floats);
   m.attr("arch") = "gfx950";
   // the attention limits ops/__init__.py repeats for its CPU path (tests hold the two together)
   m.attr("ATTN_PLAN_HDR") = attn_plan_hdr();

@@ -99,6 +99,9 @@ class TurnOutput:
     metrics: Dict[str, float]
     error: Optional[BaseException] = None
     dev_ids: Optional[torch.Tensor] = None    # ``ids`` on the engine's device (None: host only)
+    # ``params.logprobs`` set: one record (tok_lp, top_ids, top_lps) per id of ``ids`` (None for the
+    # teacher-forced tail tokens, which were never sampled)
+    logprobs: Optional[List[Optional[Tuple[float, List[int], List[float]]]]] = None
 
 
 def _dtype(s: str) -> torch.dtype:
@@ -707,7 +710,8 @@ class Engine:
         outs = []
         seen = set()
         dev_gen = getattr(self, "_dev_gen", None) or [None] * len(turns)
-        for t, s, g, n, d, key, nf, dg in zip(turns, seqs, gen, reused, deltas, keys, forced, dev_gen):
+        gen_lp = self._gen_logprobs
+        for b, (t, s, g, n, d, key, nf, dg) in enumerate(zip(turns, seqs, gen, reused, deltas, keys, forced, dev_gen)):
             text = self.tokenizer.decode(g)
             spre = 0
             if key is not None and key not in seen:     # the group's shared prefill, counted once
@@ -719,7 +723,8 @@ class Engine:
                 "decode_tokens": len(g) - nf, "forced_tokens": nf, "prefill_ms": (t1 - t0) * 1e3,
                 "decode_ms": (t2 - t1) * 1e3, "decode_tok_s": (len(g) - nf) / max(t2 - t1, 1e-9), "batch": len(turns),
                 "resident_tokens": s.length, "turn_ms": (t2 - t_start) * 1e3, "tp": self.tp.size},
-                dev_ids=dg if nf == 0 else None))   # forced tails exist only on the host
+                dev_ids=dg if nf == 0 else None,    # forced tails exist only on the host
+                **({"logprobs": gen_lp[b] + [None] * nf} if gen_lp[b] is not None else {})))
         self.stats["prefill_tokens"] += sum(len(d) for d in deltas) + sum(shared_pre.values())
         self.stats["decode_tokens"] += sum(len(g) for g in gen) - sum(forced)
         self.stats["prefill_s"] += t1 - t0
@@ -820,6 +825,8 @@ class Engine:
         for sq in seqs:     # the reply starts after the prompt; the chunked decode carries it across its calls
             sq.reply_start = sq.length
         first = self._sample_host(logits, seqs, turns).tolist()
+        for sq, rec in zip(seqs, self._first_logprobs):
+            sq.reply_logprobs = None if rec is None else [rec]
         ms = (time.perf_counter() - t0) * 1e3
         self.stats["prefill_tokens"] += sum(len(d) for d in deltas) + sum(shared_pre.values())
         self.stats["prefill_s"] += ms / 1e3
@@ -876,19 +883,24 @@ class Engine:
         # where each reply began: set by start_turns; a sequence decoded without it starts its reply at ``last``
         starts = [sq.length if sq.reply_start is None else min(sq.reply_start, sq.length) for sq in seqs]
         runner = self._agreed_graph(len(seqs), max(sq.length for sq in seqs) + steps + 1, groups is not None,
-                                    self.dist_greedy(chunk), processors=self.wants_processors(chunk))
+                                    self.dist_greedy(chunk), processors=self.wants_processors(chunk),
+                                    logprobs=self.wants_logprobs(chunk))
         with trace.range(f"decode chunk B={len(seqs)} steps={steps}"):
             if runner is not None:
                 toks = runner.run(self, seqs, chunk, first, steps + 1, time.perf_counter() + 1e9, eos, groups,
                                   reply_starts=starts)
+                lps = runner.last_logprobs if self.wants_logprobs(chunk) else None
             else:
                 toks = self._decode_eager(seqs, chunk, first, steps + 1, time.perf_counter() + 1e9, eos, groups,
                                           reply_starts=starts)
+                lps = self._eager_logprobs
         out = []
-        for sq, tk, f in zip(seqs, toks, last):
+        for b, (sq, tk, f) in enumerate(zip(seqs, toks, last)):
             new = list(tk[1:steps + 1])
             sq.tokens.extend([int(f)] + new[:-1])     # K/V now covers the old last token + all but the newest
             out.append(new)
+            if lps is not None and lps[b] is not None:      # one record per token returned
+                sq.reply_logprobs = (sq.reply_logprobs or []) + lps[b][:len(new)]
         self.stats["decode_tokens"] += sum(len(n) for n in out)
         self.stats["decode_s"] += time.perf_counter() - t0
         return out
@@ -905,7 +917,20 @@ class Engine:
         if self.wants_processors(turns):    # the first token obeys bans and penalties too (no reply yet)
             proc = ops.LogitProc(B, dev).fill([(s.tokens, s.length, t.params) for s, t in zip(seqs, turns)])
             ops.apply_logit_processors(logits, proc)
-        return ops.sample(logits, temp, top_p, top_k, seeds, offs)
+        first = ops.sample(logits, temp, top_p, top_k, seeds, offs)
+        # the first token's logprobs: the processors have run on this tensor, so these are the logits
+        # it was sampled from
+        self._first_logprobs: List[Optional[tuple]] = [None] * B
+        if self.wants_logprobs(turns):
+            lp = ops.LogProbs(B, dev).fill([t.params for t in turns])
+            ops.token_logprobs(logits, lp, ids=first)
+            self._first_logprobs = lp.records(1)[0]
+        return first
+
+    @staticmethod
+    def wants_logprobs(turns: Sequence[Turn]) -> bool:
+        """Some row of the batch asks for logprobs."""
+        return any(t.params.wants_logprobs() for t in turns)
 
     @staticmethod
     def wants_processors(turns: Sequence[Turn]) -> bool:
@@ -924,15 +949,23 @@ class Engine:
         for s, n in zip(seqs, max_new):
             self.kv.ensure_capacity(s, s.length + steps)
         eos = self.tokenizer.stop_ids
+        want_lp = self.wants_logprobs(turns)
         runner = self._agreed_graph(B, max(s.length for s in seqs) + steps, groups is not None, self.dist_greedy(turns),
-                                    processors=self.wants_processors(turns))
+                                    processors=self.wants_processors(turns), logprobs=want_lp)
         with trace.range(f"decode B={B} steps={steps}"):
             if runner is not None:
                 toks = runner.run(self, seqs, turns, first, steps, deadline, eos, groups)
                 dev_toks = runner.last_dev
+                lps = runner.last_logprobs if want_lp else None
             else:
                 toks = self._decode_eager(seqs, turns, first, steps, deadline, eos, groups)
                 dev_toks = None
+                lps = self._eager_logprobs
+        # per row: one record per kept token (the first token's from _sample_host), or None
+        first_lp = getattr(self, "_first_logprobs", None)
+        if first_lp is None or len(first_lp) != B:
+            first_lp = [None] * B
+        self._gen_logprobs: List[Optional[list]] = [None] * B
         gen: List[List[int]] = []
         self._dev_gen: List[Optional[torch.Tensor]] = []
         for b, (s, t) in enumerate(zip(seqs, turns)):
@@ -942,6 +975,8 @@ class Engine:
             if t.params.stop_on_consensus:
                 g = _cut_at_consensus(self.tokenizer, g)
             gen.append(g)
+            if t.params.wants_logprobs() and lps is not None and lps[b] is not None:
+                self._gen_logprobs[b] = ([first_lp[b]] + lps[b])[:len(g)]
             # the kept ids are a prefix of the sampled ones: their device copy is a slice
             self._dev_gen.append(dev_toks[b, :len(g)] if dev_toks is not None and len(g) <= dev_toks.shape[1]
                                  else torch.tensor(g, dtype=torch.int64).to(self.device, non_blocking=True))
@@ -996,6 +1031,9 @@ class Engine:
         # logit processors: the same op as the captured step, from host history only
         proc = ops.LogitProc(B, dev) if self.wants_processors(turns) else None
         starts = reply_starts if reply_starts is not None else [s.length for s in seqs]
+        # logprobs: the same op as the captured step's last launches, in its ``ids`` form
+        lp = ops.LogProbs(B, dev).fill([t.params for t in turns]) if self.wants_logprobs(turns) else None
+        self._eager_logprobs = None if lp is None else [None if k < 0 else [] for k in lp.wanted]
         for step in range(1, steps):
             pos = list(lens)
             slots = [s.blocks[p // self.kv.block_size] * self.kv.block_size + p % self.kv.block_size
@@ -1012,7 +1050,13 @@ class Engine:
             if dist_greedy:
                 cur = self.tp.greedy_gather(logits, self.cfg.vocab)
             else:
-                cur = ops.sample(logits.contiguous(), temp, top_p, top_k, seeds, offs)
+                logits = logits.contiguous()
+                cur = ops.sample(logits, temp, top_p, top_k, seeds, offs)
+            if lp is not None:
+                ops.token_logprobs(logits, lp, ids=cur)
+                for acc, rec in zip(self._eager_logprobs, lp.records(1)[0]):
+                    if acc is not None:
+                        acc.append(rec)
             for b, x in enumerate(cur.tolist()):
                 out[b].append(int(x))
             lens = [l + 1 for l in lens]
@@ -1052,6 +1096,8 @@ class Engine:
             return False
         if self.wants_processors(turns):    # processors need full rows: the (value, id) gather never sees them
             return False
+        if self.wants_logprobs(turns):      # so do logprobs
+            return False
         return not (self.on_gpu and self.ecfg.use_graphs and self.tp.backend() != "nccl")
 
     def k9_only_step(self) -> bool:
@@ -1060,7 +1106,8 @@ class Engine:
         os_ = self.tp.oneshot
         return os_ is not None and bool(getattr(os_, "gather_ok", False))
 
-    def _agreed_graph(self, B: int, max_ctx: int, grouped: bool, dist_greedy: bool, processors: bool = False):
+    def _agreed_graph(self, B: int, max_ctx: int, grouped: bool, dist_greedy: bool, processors: bool = False,
+                      logprobs: bool = False):
         """The captured decode step, or None (eager). A capture that fails on ANY rank of a
         tensor-parallel group sends EVERY rank to eager decode: a rank replaying a graph whose K9
         calls no peer issues would wait out each poll bound. The group agrees twice, only when the
@@ -1071,11 +1118,13 @@ class Engine:
         fallback re-agrees them (:meth:`_resync_k9`).
 
         ``processors``: the variant whose step applies the logit processors before K6. It is cached
-        beside the plain graph under ``(key, "proc")``; batches without processors never see it."""
+        beside the plain graph under ``(key, "proc")``; batches without processors never see it.
+        ``logprobs``: the variant whose step ends with the logprob launches, under ``(key, "lp")`` or
+        ``(key, "proc", "lp")``; batches without logprobs never see it."""
         if not (self.on_gpu and self.ecfg.use_graphs):
             return None
         key = self._graph_key(B, grouped, dist_greedy)
-        ckey = (key, "proc") if processors else key
+        ckey = self._cache_key(key, processors, logprobs)
         g = self.graphs.get(ckey)
         if g is not None:
             return g
@@ -1084,7 +1133,8 @@ class Engine:
         try:
             with failsafe.stage("capture"):     # the plain graph is constructed exactly as before the flag existed
                 g = DecodeGraph(self, key[0], key[1], grouped=grouped, dist_greedy=dist_greedy, capture=False,
-                                **({"processors": True} if processors else {}))
+                                **({"processors": True} if processors else {}),
+                                **({"logprobs": True} if logprobs else {}))
         except RuntimeError as e:   # out of memory for the graph's static buffers
             err = e
         failed = self.tp.any_rank(err is not None) if self.tp.size > 1 else err is not None
@@ -1117,14 +1167,21 @@ class Engine:
         bucket = next((b for b in BATCH_BUCKETS if b >= B), B)
         return (bucket, ops.decode_splits(bucket, self.model.n_kv_heads, grouped=grouped), grouped, dist_greedy)
 
+    @staticmethod
+    def _cache_key(key, processors: bool, logprobs: bool):
+        """The plain key, ``(key, "proc")``, ``(key, "lp")`` or ``(key, "proc", "lp")``."""
+        tags = (("proc",) if processors else ()) + (("lp",) if logprobs else ())
+        return (key, *tags) if tags else key
+
     def _graph_for(self, B: int, max_ctx: int, grouped: bool = False, dist_greedy: bool = False,
-                   processors: bool = False) -> "DecodeGraph":
+                   processors: bool = False, logprobs: bool = False) -> "DecodeGraph":
         from .graphs import DecodeGraph
         key = self._graph_key(B, grouped, dist_greedy)
-        ckey = (key, "proc") if processors else key
+        ckey = self._cache_key(key, processors, logprobs)
         g = self.graphs.get(ckey)
         if g is None:
-            g = DecodeGraph(self, key[0], key[1], grouped=grouped, dist_greedy=dist_greedy, processors=processors)
+            g = DecodeGraph(self, key[0], key[1], grouped=grouped, dist_greedy=dist_greedy, processors=processors,
+                            **({"logprobs": True} if logprobs else {}))
             self.graphs[ckey] = g
             self.stats["graph_captures"] = self.stats.get("graph_captures", 0) + 1
         return g

@@ -55,7 +55,7 @@ def no_gc_during_capture():
 
 class DecodeGraph:
     def __init__(self, engine, bucket: int, splits: int, grouped: bool = False, dist_greedy: bool = False,
-                 capture: bool = True, processors: bool = False):
+                 capture: bool = True, processors: bool = False, logprobs: bool = False):
         self.engine = engine
         self.B = bucket
         self.splits = splits
@@ -96,6 +96,11 @@ class DecodeGraph:
         # their static operands; the captured kernel reads the reply so far from ``out`` / ``step``
         assert not (processors and dist_greedy), "the (value, id) gather never sees processed rows"
         self.proc = ops.LogitProc(B, dev) if processors else None
+        # logprobs: such a graph owns the per-row request, the kernels' workspace and one record row per
+        # step; its last two launches fill record row step - 1 after K6 has chosen out[step - 1]
+        assert not (logprobs and dist_greedy), "the (value, id) gather never sees full rows"
+        self.lp = ops.LogProbs(B, dev, MAX_STEPS) if logprobs else None
+        self.last_logprobs = None
         self.graph = None
         self._host_out: List[torch.Tensor] = []
         if capture:     # (Engine._agreed_graph agrees on the buffers first, then captures)
@@ -142,6 +147,7 @@ class DecodeGraph:
             ops.sample_advance(logits.contiguous(), self.temp, self.top_p, self.top_k, self.seeds, offsets,
                                self.sample_ws, self.nxt, self.out, self.input_ids, self.positions, self.ctx_lens,
                                self.step, self.slots, self.hidden, self.block_tables, e.model.w["embed"], self.bs)
+            self._logprobs(logits)
             return
         if self.dist_greedy:
             nxt = e.tp.greedy_gather(logits, e.cfg.vocab)
@@ -155,6 +161,13 @@ class DecodeGraph:
                                      e.model.w["embed"], self.bs))
         else:
             ops.decode_advance(self.out, self.input_ids, self.positions, self.ctx_lens, self.step, nxt)
+        self._logprobs(logits)
+
+    def _logprobs(self, logits: torch.Tensor) -> None:
+        """The step's LAST launches: logprobs of the token K6 just recorded, on the logits it sampled
+        from (K6 reads them only; so do these)."""
+        if self.lp is not None:
+            ops.token_logprobs(logits.contiguous(), self.lp, out=self.out, step=self.step)
 
     def _host_buffer(self, k: int) -> torch.Tensor:
         """Pinned [MAX_STEPS, B] int64 copy targets of the sampled ids (two, alternating)."""
@@ -238,6 +251,8 @@ class DecodeGraph:
             starts = reply_starts if reply_starts is not None else [s.length for s in seqs]
             self.proc.fill([(s.tokens + [f], r, t.params) for s, f, r, t in zip(seqs, first_host, starts, turns)]
                            + [None] * pad)
+        if self.lp is not None:
+            self.lp.fill([t.params for t in turns] + [None] * pad)
         with torch.no_grad():
             self._prep()
         need_tokens = any((not t.params.ignore_eos) or t.params.stop_on_consensus for t in turns)
@@ -282,4 +297,8 @@ class DecodeGraph:
         # a copy: the next turn's replays overwrite ``out``
         self.last_dev = torch.cat([first[:B].view(1, B), self.out[:n, :B]], 0).t().contiguous()
         got = self.out[:n, :B].t().tolist() if n > 0 else [[] for _ in range(B)]
+        if self.lp is not None:
+            # per row, one (tok_lp, top_ids, top_lps) per token sampled in the graph (None: row did not ask)
+            recs = self.lp.records(n) if n > 0 else []
+            self.last_logprobs = [None if self.lp.wanted[b] < 0 else [r[b] for r in recs] for b in range(B)]
         return [[f] + g for f, g in zip(first_host, got)]

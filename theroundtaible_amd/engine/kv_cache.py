@@ -60,6 +60,10 @@ class SeqState:
     # index in ``tokens`` at which the current reply starts (Engine.start_turns; None: not decoding
     # in chunks) — the logit processors count a reply's tokens across continue_decode calls
     reply_start: Optional[int] = None
+    # logprob records (tok_lp, top_ids, top_lps) of the current reply's tokens, one per sampled token:
+    # Engine.start_turns sets it ([first token's record], or None when the turn does not ask),
+    # continue_decode extends it by one record per token it returns
+    reply_logprobs: Optional[list] = None
 
     @property
     def length(self) -> int:

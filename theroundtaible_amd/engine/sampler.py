@@ -6,6 +6,7 @@ from typing import Dict, Optional
 from dataclasses import dataclass
 
 MAX_LOGIT_BIAS = 300     # OpenAI's limit; ops.LOGIT_PROC_MAX_BIAS
+MAX_TOP_LOGPROBS = 20    # OpenAI's limit; ops.MAX_TOP_LOGPROBS
 
 
 @dataclass
@@ -26,6 +27,21 @@ class SamplingParams:
     presence_penalty: float = 0.0       # OpenAI form, over the tokens of this reply
     frequency_penalty: float = 0.0      # OpenAI form, times the token's count in this reply
     logit_bias: Optional[Dict[int, float]] = None   # {token id: bias}, at most 300 entries in [-100, 100]
+    # logprobs (csrc/logprobs.hip): None = off; n in 0..20 = every sampled token's log-probability plus
+    # the n most likely alternatives, on the logits as sampled from (after the processors above,
+    # before temperature / top-k / top-p). Never changes the sampled ids.
+    logprobs: Optional[int] = None
+
+    def wants_logprobs(self) -> bool:
+        return self.logprobs is not None
+
+    def check_logprobs(self) -> None:
+        """ValueError for a ``logprobs`` outside 0..20 (serve.py answers 400)."""
+        n = self.logprobs
+        if n is None:
+            return
+        if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= MAX_TOP_LOGPROBS:
+            raise ValueError(f"logprobs must be an integer in 0..{MAX_TOP_LOGPROBS}, got {n!r}")
 
     def has_processors(self) -> bool:
         """False when every processor field is neutral: such a row is sampled exactly as before."""

@@ -707,3 +707,62 @@ def apply_logit_processors(logits: torch.Tensor, proc: LogitProc, out: Optional[
                             proc.bias_tok, proc.bias_val, proc.bias_n, out if step is not None else None, step)
         return logits
     return ref.apply_logit_processors(logits, proc, out, step)
+
+
+MAX_TOP_LOGPROBS = ref.MAX_TOP_LOGPROBS          # alternatives a row can ask for
+
+
+class LogProbs:
+    """Static operands and records of :func:`token_logprobs` for ``batch`` rows and ``steps`` record
+    rows: ``n_top`` [B] int32 (-1: the row does not ask, the default), the kernels' workspace, and
+    the records ``tok_lp`` [steps, B] fp32, ``top_id`` [steps, B, 20] int32, ``top_lp``
+    [steps, B, 20] fp32. A decode graph owns one and refills ``n_top`` per turn; the captured
+    kernels read and write these addresses."""
+
+    def __init__(self, batch: int, device, steps: int = 1):
+        self.n_top = torch.full((batch,), -1, dtype=torch.int32, device=device)
+        self.ws = torch.zeros(batch * ref.LOGPROB_WS_ROW, dtype=torch.float32, device=device)
+        self.tok_lp = torch.zeros(max(1, steps), batch, dtype=torch.float32, device=device)
+        self.top_id = torch.full((max(1, steps), batch, MAX_TOP_LOGPROBS), -1, dtype=torch.int32, device=device)
+        self.top_lp = torch.full((max(1, steps), batch, MAX_TOP_LOGPROBS), float("-inf"), dtype=torch.float32,
+                                 device=device)
+        self.wanted: list = [-1] * batch
+
+    def fill(self, rows) -> "LogProbs":
+        """``rows``: per batch row an object with the SamplingParams field ``logprobs`` (None: off,
+        n: the chosen token's logprob plus n alternatives), or None for a row that does not ask."""
+        want = [-1] * self.n_top.numel()
+        for b, p in enumerate(rows):
+            n = None if p is None else getattr(p, "logprobs", None)
+            if n is not None:
+                if not 0 <= int(n) <= MAX_TOP_LOGPROBS:
+                    raise ValueError(f"logprobs must be in 0..{MAX_TOP_LOGPROBS}, got {n}")
+                want[b] = int(n)
+        self.wanted = want
+        self.n_top.copy_(torch.tensor(want, dtype=torch.int32).to(self.n_top.device, non_blocking=True))
+        return self
+
+    def records(self, n: int = 1):
+        """The first ``n`` record rows on the host: per step, per row, ``(tok_lp, top_ids, top_lps)``
+        cut to the row's ``n_top``, or None for a row that did not ask."""
+        tok = self.tok_lp[:n].cpu().tolist()
+        ids = self.top_id[:n].cpu().tolist()
+        lps = self.top_lp[:n].cpu().tolist()
+        return [[None if k < 0 else (tok[s][b], ids[s][b][:k], lps[s][b][:k]) for b, k in enumerate(self.wanted)]
+                for s in range(len(tok))]
+
+
+def token_logprobs(logits: torch.Tensor, lp: LogProbs, ids: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None, step: Optional[torch.Tensor] = None) -> LogProbs:
+    """The chosen token's log-probability and the ``n_top`` most likely tokens of each row of
+    ``logits`` [B, V] (bf16 or fp32, row stride >= V; only read) into ``lp``'s records, on the
+    logits as the sampler saw them: after the logit processors, before temperature / top-k / top-p
+    (csrc/logprobs.hip; semantics: ops/reference.py). ``ids`` [B] int64: the chosen tokens, record
+    row 0. With the graph's ``out`` [steps, B] and device ``step`` the call is capturable, sits
+    AFTER the step's sample and advance, and writes record row ``step - 1`` for ``out[step - 1]``."""
+    if (out is None) != (step is None) or (ids is None) == (step is None):
+        raise ValueError("token_logprobs takes either ids or (out, step)")
+    if _use_native(logits):
+        native().token_logprobs(logits, lp.n_top, lp.ws, lp.tok_lp, lp.top_id, lp.top_lp, ids, out, step)
+        return lp
+    return ref.token_logprobs(logits, lp, ids, out, step)

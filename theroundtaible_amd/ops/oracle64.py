@@ -20,6 +20,8 @@ fp32 error (unit round-off 2^-24) that is far below a bf16 ulp except where term
   ``- fp * c``, ``- pp`` reaches: the kernel rounds the product and each of the four steps to fp32,
   five roundings of at most 2^-24 * mag each (a division by rp < 1 scales the error carried so
   far by 1 / rp, and the step's magnitude with it), so 2^-22 * mag bounds their sum with 1.6x margin.
+* logprobs (csrc/logprobs.hip): ``2^-21 * (1 + |l| + |lse|)`` on fp32 values, ids exactly; the
+  slack is measured, not derived: 4x the fp32 CPU reference's own worst error (see LOGPROB_SLACK).
 
 The input builders of the CPU emulation test and the GPU test live here too, so both see the
 same bits.
@@ -409,3 +411,141 @@ def logit_proc_case(V: int, dtype: torch.dtype, n_hist: int, step: int, seed: in
     proc.bias_n[2] = nb
     out = torch.stack([draw(LOGIT_PROC_OUT_ROWS) for _ in range(B)], dim=1).to(torch.int64).contiguous()
     return logits, proc, out, torch.tensor([step], dtype=torch.int64)
+
+
+# ---- logprobs (csrc/logprobs.hip) ------------------------------------------------------------------
+# Tolerance: |lp - e| <= LOGPROB_SLACK * (1 + |l| + |lse|), lp compared as fp32, l the token's stored
+# logit. lp = l - lse is one fp32 subtraction of two numbers of those magnitudes, after an lse whose
+# error is a few fp32 roundings of |lse| plus the relative error of the sum. The slack is the worst
+# ratio of the fp32 REFERENCE (ops/reference.py, torch logsumexp) against this oracle over every case
+# of LOGPROB_KINDS x LOGPROB_V x {bf16, fp32} plus the B = 32 case, measured on the CPU
+# (LOGPROB_REF_WORST), times 4 for the device's expf / logf and its chunked summation order, rounded
+# up to a power of two. It is not tuned against the kernel.
+LOGPROB_REF_WORST = 8.11e-8      # measured (tests/test_logprobs_cpu.py::test_reference_vs_oracle prints it)
+LOGPROB_SLACK = 2.0 ** -21       # 4 * 8.11e-8 = 3.24e-7 <= 2^-21 = 4.77e-7
+MAX_TOP_LOGPROBS = 20
+LOGPROB_V = (19, 1003, 4096, 4097, 32064)
+LOGPROB_V_BIG = 152064            # 38 chunks, one case
+LOGPROB_KINDS = ("random", "equal", "levels8", "top_one_chunk", "top_spread", "last", "big80", "banned300",
+                 "finite5")
+
+
+def token_logprobs(logits: torch.Tensor, n_top, toks):
+    """fp64 twin of ops.token_logprobs on the exact stored values: ``(tok_lp [B], top_id [B, 20],
+    top_lp [B, 20], lse [B], l_tok [B], l_top [B, 20])``. Ids are decided exactly (a stable sort of
+    the stored values: value descending, token id ascending). Rows with ``n_top < 0`` hold NaN / -2
+    (never compared). Written apart from ops/reference.py: max-shifted sum in fp64, not logsumexp."""
+    B, V = logits.shape
+    K = MAX_TOP_LOGPROBS
+    tok_lp = torch.full((B,), float("nan"), dtype=torch.float64)
+    top_id = torch.full((B, K), -2, dtype=torch.int64)
+    top_lp = torch.full((B, K), float("nan"), dtype=torch.float64)
+    lse = torch.full((B,), float("nan"), dtype=torch.float64)
+    l_tok = torch.zeros(B, dtype=torch.float64)
+    l_top = torch.zeros(B, K, dtype=torch.float64)
+    for b in range(B):
+        nt = min(int(n_top[b]), K)
+        if nt < 0:
+            continue
+        l = logits[b].detach().cpu().double() + 0.0
+        m = l.max()
+        lse[b] = m + torch.log(torch.exp(l - m).sum()) if bool(torch.isfinite(m)) else m
+        order = torch.argsort(l, descending=True, stable=True)
+        k = min(nt, V)
+        top_id[b] = -1
+        top_lp[b] = float("-inf")
+        top_id[b, :k] = order[:k]
+        l_top[b, :k] = torch.where(torch.isfinite(l[order[:k]]), l[order[:k]], torch.zeros(k, dtype=torch.float64))
+        top_lp[b, :k] = l[order[:k]] - lse[b]
+        t = int(toks[b])
+        if 0 <= t < V:
+            tok_lp[b] = l[t] - lse[b]
+            l_tok[b] = l[t] if bool(torch.isfinite(l[t])) else 0.0
+    return tok_lp, top_id, top_lp, lse, l_tok, l_top
+
+
+def logprob_tol(e, l_tok, lse, dtype: torch.dtype = torch.bfloat16):
+    """Tolerance of the logprob ``e`` of a token whose stored logit is ``l_tok`` (0 where it is not
+    finite: such an ``e`` is -inf or NaN and compared by position). The same for both dtypes: the
+    stored logit is exact in fp32 either way."""
+    return LOGPROB_SLACK * (1.0 + l_tok.double().abs() + lse.double().abs()) * torch.ones_like(e, dtype=torch.float64)
+
+
+def logprob_ntop(B: int) -> torch.Tensor:
+    """B = 3: (-1, 0, 20); larger batches mix off rows, 0, 1, 5, 19 and 20."""
+    mix = (-1, 0, 20, 5, 1, 19, -1, 20, 7)
+    return torch.tensor([mix[b % len(mix)] for b in range(B)], dtype=torch.int32)
+
+
+def logprob_case(V: int, dtype: torch.dtype, kind: str, seed: int = 0, B: int = 3, ld: Optional[int] = None):
+    """-> (logits [B, V] of ``dtype``, a view of NaN-padded rows ``ld`` apart when ``ld`` is given;
+    n_top [B] int32; toks [B] int64, the chosen tokens). Kinds: LOGPROB_KINDS.
+
+    random: N(0, 4). equal: one value everywhere. levels8: 8 bf16 levels, ties at every cut.
+    top_one_chunk / top_spread: the 20 largest inside the last chunk / one per chunk, round robin.
+    last: the maximum and the chosen token at V - 1. big80: around +-80 (fp32 overflows without the
+    max subtraction). banned300: 300 tokens at -inf, the chosen one among them. finite5: 5 finite.
+    With B > 3 two chosen ids lie outside [0, V)."""
+    g = _gen(77000 + 31 * V + 1009 * seed + 7 * LOGPROB_KINDS.index(kind) + (dtype == torch.float32) + 13 * B)
+    CH = 4096
+    x = 4.0 * torch.randn(B, V, generator=g)
+    toks = torch.randint(0, V, (B,), generator=g)
+    if kind == "equal":
+        x = torch.full((B, V), 1.625)
+    elif kind == "levels8":
+        lv = torch.tensor([-3.5, -0.0, 0.0, 2.75, 2.765625, -11.0, 0.40625, 2.75])
+        x = lv[torch.randint(0, 8, (B, V), generator=g)]
+    elif kind in ("top_one_chunk", "top_spread"):
+        nch = (V + CH - 1) // CH
+        for b in range(B):
+            if kind == "top_one_chunk":
+                lo = (nch - 1) * CH
+                pos = lo + torch.randperm(V - lo, generator=g)[:MAX_TOP_LOGPROBS]
+            else:
+                pos = torch.tensor([(j % nch) * CH + int(torch.randint(0, min(CH, V - (j % nch) * CH), (1,),
+                                                                         generator=g)) for j in range(MAX_TOP_LOGPROBS)])
+            x[b, pos] = 30.0 + 0.5 * torch.arange(pos.numel(), dtype=torch.float32)
+    elif kind == "last":
+        x[:, V - 1] = 40.0
+        toks[:] = V - 1
+    elif kind == "big80":
+        x = 80.0 * torch.sign(torch.randn(B, V, generator=g)) + torch.randn(B, V, generator=g)
+    elif kind == "banned300":
+        for b in range(B):
+            ban = torch.randperm(V, generator=g)[:min(300, V - 1)]
+            x[b, ban] = float("-inf")
+            toks[b] = ban[0]
+    elif kind == "finite5":
+        for b in range(B):
+            keep = torch.randperm(V, generator=g)[:5]
+            v = x[b, keep].clone()
+            x[b] = float("-inf")
+            x[b, keep] = v
+    if B > 3:
+        toks[B - 1], toks[B - 2] = V, -1
+    n_top = logprob_ntop(B)
+    if ld is None:
+        return x.to(dtype), n_top, toks.to(torch.int64)
+    store = torch.full((B, ld), float("nan"), dtype=dtype)
+    store[:, :V] = x.to(dtype)
+    return store[:, :V], n_top, toks.to(torch.int64)
+
+
+def assert_logprobs(tok_lp, top_id, top_lp, oracle, n_top, what: str = "") -> float:
+    """One record row ``tok_lp`` [B], ``top_id`` / ``top_lp`` [B, 20] against :func:`token_logprobs`'s
+    result: ids exactly, values within :func:`logprob_tol`, -inf / NaN in place, over the rows
+    with ``n_top >= 0``. Returns the worst error / tolerance."""
+    e_tok, e_id, e_lp, lse, l_tok, l_top = oracle
+    rows = torch.as_tensor(n_top).cpu() >= 0
+    if not bool(rows.any()):
+        return 0.0
+    got_id = top_id.detach().cpu().long()[rows]
+    bad = got_id != e_id[rows]
+    assert not bool(bad.any()), (f"{what}: top ids differ at {bad.nonzero()[0].tolist()} (of the asking rows): "
+                                 f"got {got_id[bad][0].item()}, oracle {e_id[rows][bad][0].item()}")
+    r1 = assert_within(tok_lp.detach().cpu()[rows], e_tok[rows], logprob_tol(e_tok[rows], l_tok[rows], lse[rows]),
+                       what + " tok_lp", dtype=torch.float32)
+    r2 = assert_within(top_lp.detach().cpu()[rows], e_lp[rows],
+                       logprob_tol(e_lp[rows], l_top[rows], lse[rows][:, None]), what + " top_lp",
+                       dtype=torch.float32)
+    return max(r1, r2)

@@ -493,3 +493,48 @@ def apply_logit_processors(logits: torch.Tensor, proc, out=None, step=None) -> t
                 l = l - pp
             logits[b, t] = l.to(logits.dtype)
     return logits
+
+
+# ---- logprobs (csrc/logprobs.hip) ------------------------------------------------------------------
+
+MAX_TOP_LOGPROBS = 20                 # alternatives a row can ask for (OpenAI's limit)
+LOGPROB_CHUNK = 4096                  # csrc/logprobs_plan.h: elements per chunk, at most 64 chunks
+LOGPROB_WS_ROW = 64 * 44              # workspace words per row, whatever V is
+
+
+def logprob_step(ids=None, out=None, step=None):
+    """-> (chosen tokens, record row) of a logprob call, or None when the graph form's step is
+    outside the record: ``ids`` form -> row 0; ``(out, step)`` form -> the token K6 just recorded,
+    ``out[step - 1]``, and row ``step - 1``."""
+    if step is not None and out is not None:
+        s = int(step.reshape(-1)[0]) - 1
+        return (out[s], s) if 0 <= s < out.shape[0] else None
+    return ids, 0
+
+
+def token_logprobs(logits: torch.Tensor, lp, ids=None, out=None, step=None):
+    """Semantics of csrc/logprobs.hip in fp32: per row with ``n_top >= 0``, on the logits as sampled
+    from (l = the stored value as fp32), ``lse = logsumexp(l)``, the chosen token's ``l - lse``
+    (NaN for an id outside [0, V)) and the ``n_top`` largest l, value descending then token id
+    ascending (a stable sort), each with ``l - lse``; entries past min(n_top, V): id -1, lp -inf.
+    Rows with ``n_top < 0`` write nothing. The logits are only read."""
+    at = logprob_step(ids, out, step)
+    if at is None:
+        return lp
+    toks, rec = at
+    B, V = logits.shape
+    for b in range(B):
+        nt = min(int(lp.n_top[b]), MAX_TOP_LOGPROBS)
+        if nt < 0:
+            continue
+        l = logits[b].detach().float() + 0.0        # -0.0 ties with +0.0
+        lse = torch.logsumexp(l, 0)
+        vals, idx = torch.sort(l, descending=True, stable=True)      # stable: equal values keep id order
+        k = min(nt, V)
+        lp.top_id[rec, b] = -1
+        lp.top_lp[rec, b] = float("-inf")
+        lp.top_id[rec, b, :k] = idx[:k].to(torch.int32)
+        lp.top_lp[rec, b, :k] = vals[:k] - lse
+        t = int(toks[b])
+        lp.tok_lp[rec, b] = (l[t] - lse) if 0 <= t < V else float("nan")
+    return lp

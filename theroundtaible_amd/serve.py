@@ -35,6 +35,7 @@ from __future__ import annotations
 
 import itertools
 import json
+import math
 import os
 import queue
 import sys
@@ -47,6 +48,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 from .engine import Engine, EngineConfig, SamplingParams, Turn
 from .engine.engine import cut_at_stop
+from .engine.sampler import MAX_TOP_LOGPROBS
 from .utils import failsafe
 
 ROLE_TAGS = {"system": "Systeem", "user": "Gebruiker", "assistant": "Assistent"}
@@ -134,9 +136,12 @@ class _Request:
     stream_q: Optional["queue.Queue"] = None
     cancelled: bool = False        # the streaming client went away: stop decoding it
     stops: Tuple[str, ...] = ()    # OpenAI "stop" / Ollama options.stop strings
+    stream_lp: Optional[list] = None    # logprob records of (at least) the ids published so far
 
-    def publish(self, gen: List[int]) -> None:
+    def publish(self, gen: List[int], logprobs: Optional[list] = None) -> None:
         if self.stream_q is not None:
+            if logprobs is not None:
+                self.stream_lp = list(logprobs)     # before the ids: the reader takes it after them
             self.stream_q.put(list(gen))
 
 
@@ -236,7 +241,10 @@ class Scheduler:
             if r.stops:
                 text, hit = cut_at_stop_strings(text, r.stops)
                 m["stop_string"] = hit
-            r.result = _Output(text, gen, m)
+            lps = getattr(a.seq, "reply_logprobs", None) if r.params.wants_logprobs() else None
+            # one record per kept id (with a stop string the list covers the kept ids, so it may run a
+            # few tokens past the cut text)
+            r.result = _Output(text, gen, m, logprobs=None if lps is None else list(lps[:len(gen)]))
             with self._lock:
                 self.stats["requests"] += 1
                 self.stats["prompt_tokens"] += int(m.get("prompt_tokens", 0))
@@ -272,7 +280,7 @@ class Scheduler:
                         self.stats["admitted_midflight"] += len(started)
                 for r, t, (sq, first, m) in zip(new, turns, started):
                     a = _Active(r, sq, t, [first], dict(m, batch=0), time.perf_counter())
-                    r.publish(a.gen)
+                    r.publish(a.gen, sq.reply_logprobs)
                     if self._finished(a):
                         self._complete(a)
                     else:
@@ -292,7 +300,7 @@ class Scheduler:
                 a.gen.extend(toks)
                 a.metrics["batch"] = max(a.metrics.get("batch", 0), len(active))
                 if not self._finished(a):          # a finished request's text comes with its result
-                    a.req.publish(a.gen)
+                    a.req.publish(a.gen, a.seq.reply_logprobs)
             with self._lock:
                 self.stats["batches"] += 1
                 self.stats["decode_steps"] += max(1, steps)
@@ -438,6 +446,7 @@ class _Output:
     text: str
     ids: List[int]
     metrics: Dict[str, Any]
+    logprobs: Optional[list] = None     # one (tok_lp, top_ids, top_lps) per id when the request asked
 
 
 class RoundtableServer:
@@ -505,6 +514,20 @@ class RoundtableServer:
                 if first is not None:
                     emit(first)
                 sent = ""
+                want_lp = r.params.wants_logprobs()
+                n_lp, off = 0, 0        # ids whose logprob entries went out, and their text offset
+
+                def entries(ids, recs):
+                    """The entries of ids[n_lp:] (each id's go out once, with the piece that first
+                    publishes it); concatenated they equal the non-streamed list."""
+                    nonlocal n_lp, off
+                    new, lps = ids[n_lp:], (recs or [])[n_lp:len(ids)]
+                    new = new[:len(lps)]
+                    got = server.logprobs_json(new, lps, chat=sse_chat, offset=off)
+                    n_lp += len(new)
+                    off += sum(len(server.token_text(t)) for t in new)
+                    return got
+                sse_chat = getattr(delta, "chat", False)
                 deadline = time.monotonic() + server.sched.timeout_s + 30
                 while True:
                     try:
@@ -516,11 +539,17 @@ class RoundtableServer:
                         break
                     text = server.visible_text(ids, r.params, r.stops)
                     if text.startswith(sent) and len(text) > len(sent):
-                        emit(delta(text[len(sent):]))
+                        if want_lp:
+                            emit(delta(text[len(sent):], entries(server.kept_ids(ids, r.params), r.stream_lp)))
+                        else:
+                            emit(delta(text[len(sent):]))
                         sent = text
                 if r.error is None and r.result is not None:
                     final = r.result.text
-                    if final.startswith(sent) and len(final) > len(sent):
+                    grows = final.startswith(sent) and len(final) > len(sent)
+                    if want_lp and (grows or n_lp < len(r.result.ids)):
+                        emit(delta(final[len(sent):] if grows else "", entries(r.result.ids, r.result.logprobs)))
+                    elif grows:
                         emit(delta(final[len(sent):]))
                     emit(last(r.result, r))
                 else:
@@ -579,12 +608,21 @@ class RoundtableServer:
                 if not isinstance(msgs, list) or not msgs:
                     raise ValueError("'messages' must be a non-empty list")
                 rid = f"chatcmpl-{uuid.uuid4().hex[:24]}"
+                if body.get("logprobs") is not None and not isinstance(body["logprobs"], bool):
+                    raise ValueError("'logprobs' must be a boolean here (and 'top_logprobs' an integer in 0..20)")
                 if body.get("stream"):
                     base = {"id": rid, "object": "chat.completion.chunk", "created": int(time.time()),
                             "model": server.model_name}
 
-                    def piece(delta, finish=None):
-                        return dict(base, choices=[{"index": 0, "delta": delta, "finish_reason": finish}])
+                    def piece(delta, finish=None, lp=None):
+                        choice = {"index": 0, "delta": delta, "finish_reason": finish}
+                        if lp is not None:
+                            choice["logprobs"] = lp
+                        return dict(base, choices=[choice])
+
+                    def delta(t, lp=None):
+                        return piece({"content": t}, lp=lp)
+                    delta.chat = True
                     include_usage = bool((body.get("stream_options") or {}).get("include_usage"))
 
                     def last(out, r):
@@ -594,16 +632,16 @@ class RoundtableServer:
                             end["usage"] = server.usage(out)
                         return end
                     self._stream(server.chat_prompt(msgs), body, body.get("user") or body.get("session"),
-                                 first=piece({"role": "assistant", "content": ""}),
-                                 delta=lambda t: piece({"content": t}), last=last)
+                                 first=piece({"role": "assistant", "content": ""}), delta=delta, last=last)
                     return
                 out, r = server.generate(server.chat_prompt(msgs), body, body.get("user") or body.get("session"))
                 usage = server.usage(out)
+                choice = {"index": 0, "message": {"role": "assistant", "content": out.text},
+                          "finish_reason": server.finish(out, r)}
+                if out.logprobs is not None:     # the key exists only when the request asked for it
+                    choice["logprobs"] = server.logprobs_json(out.ids, out.logprobs, chat=True)
                 self._send(200, {"id": rid, "object": "chat.completion", "created": int(time.time()),
-                                 "model": server.model_name,
-                                 "choices": [{"index": 0, "message": {"role": "assistant", "content": out.text},
-                                              "finish_reason": server.finish(out, r)}],
-                                 "usage": usage})
+                                 "model": server.model_name, "choices": [choice], "usage": usage})
 
             def _completion_openai(self, body):
                 prompt = body.get("prompt")
@@ -611,20 +649,32 @@ class RoundtableServer:
                     prompt = "".join(str(p) for p in prompt)
                 if not isinstance(prompt, str):
                     raise ValueError("'prompt' must be a string")
+                if body.get("logprobs") is not None:
+                    if isinstance(body["logprobs"], bool) or not isinstance(body["logprobs"], int):
+                        raise ValueError("'logprobs' must be an integer in 0..20 here")
+                    if body.get("top_logprobs") is not None:
+                        raise ValueError("'top_logprobs' belongs to /v1/chat/completions; here 'logprobs' is the count")
+                    if body.get("echo"):
+                        raise ValueError("'echo' with 'logprobs' (prompt logprobs) is not supported")
                 if body.get("stream"):
                     base = {"id": f"cmpl-{uuid.uuid4().hex[:24]}", "object": "text_completion",
                             "created": int(time.time()), "model": server.model_name}
 
-                    def piece(text, finish=None):
-                        return dict(base, choices=[{"index": 0, "text": text, "finish_reason": finish}])
+                    def piece(text, lp=None, finish=None):
+                        choice = {"index": 0, "text": text, "finish_reason": finish}
+                        if lp is not None:
+                            choice["logprobs"] = lp
+                        return dict(base, choices=[choice])
                     self._stream(prompt, body, body.get("user"), first=None, delta=piece,
-                                 last=lambda out, r: piece("", server.finish(out, r)))
+                                 last=lambda out, r: piece("", finish=server.finish(out, r)))
                     return
                 out, r = server.generate(prompt, body, body.get("user"))
+                choice = {"index": 0, "text": out.text, "finish_reason": server.finish(out, r)}
+                if out.logprobs is not None:     # the key exists only when the request asked for it
+                    choice["logprobs"] = server.logprobs_json(out.ids, out.logprobs, chat=False)
                 self._send(200, {"id": f"cmpl-{uuid.uuid4().hex[:24]}", "object": "text_completion",
                                  "created": int(time.time()), "model": server.model_name,
-                                 "choices": [{"index": 0, "text": out.text, "finish_reason": server.finish(out, r)}],
-                                 "usage": server.usage(out)})
+                                 "choices": [choice], "usage": server.usage(out)})
 
             def _chat_ollama(self, body):
                 msgs = body.get("messages")
@@ -710,9 +760,57 @@ class RoundtableServer:
                                 repetition_penalty=num("repetition_penalty", 1.0, float),
                                 repeat_last_n=num("repeat_last_n", 64, int),
                                 presence_penalty=num("presence_penalty", 0.0, float),
-                                frequency_penalty=num("frequency_penalty", 0.0, float), logit_bias=bias or None)
+                                frequency_penalty=num("frequency_penalty", 0.0, float), logit_bias=bias or None,
+                                logprobs=self.logprob_request(body))
         params.check_processors(int(self.engine.cfg.vocab))      # ValueError -> HTTP 400
+        params.check_logprobs()
         return params
+
+    @staticmethod
+    def logprob_request(body: Dict[str, Any]) -> Optional[int]:
+        """SamplingParams.logprobs of a request: the chat form ``logprobs: true`` with
+        ``top_logprobs: 0..20`` (absent: 0), or the completions form ``logprobs: 0..20``. None when
+        the request does not ask. ValueError (HTTP 400) for ``top_logprobs`` without
+        ``logprobs: true`` and for values outside the range."""
+        v, top = body.get("logprobs"), body.get("top_logprobs")
+        if top is not None and (isinstance(top, bool) or not isinstance(top, int) or not 0 <= top <= MAX_TOP_LOGPROBS):
+            raise ValueError(f"'top_logprobs' must be an integer in 0..{MAX_TOP_LOGPROBS}")
+        if isinstance(v, bool):
+            if top is not None and not v:
+                raise ValueError("'top_logprobs' requires 'logprobs': true")
+            return (top or 0) if v else None
+        if v is None:
+            if top is not None:
+                raise ValueError("'top_logprobs' requires 'logprobs': true")
+            return None
+        if not isinstance(v, int) or not 0 <= v <= MAX_TOP_LOGPROBS:
+            raise ValueError(f"'logprobs' must be an integer in 0..{MAX_TOP_LOGPROBS}")
+        return v
+
+    def token_text(self, tok: int) -> str:
+        return self.engine.tokenizer.decode([int(tok)])
+
+    def logprobs_json(self, ids: List[int], recs: List[Any], chat: bool, offset: int = 0) -> Dict[str, Any]:
+        """The response's ``logprobs`` object for ``ids`` and their records: the chat shape
+        ``{"content": [{token, logprob, bytes, top_logprobs: [{token, logprob, bytes}]}]}`` or the
+        legacy completions shape (tokens, token_logprobs, top_logprobs, text_offset from ``offset``).
+        ``token`` is the tokenizer's decoding of that single id; -inf is serialised as -9999.0
+        (OpenAI's convention: JSON has no infinity)."""
+        def num(v):
+            v = float(v)
+            return v if math.isfinite(v) else -9999.0
+
+        def entry(tok, lp):
+            text = self.token_text(tok)
+            return {"token": text, "logprob": num(lp), "bytes": list(text.encode("utf-8"))}
+        if chat:
+            return {"content": [dict(entry(t, rec[0]), top_logprobs=[entry(i, l) for i, l in zip(rec[1], rec[2])])
+                                for t, rec in zip(ids, recs)]}
+        texts = [self.token_text(t) for t in ids[:len(recs)]]
+        offs = [offset + sum(len(x) for x in texts[:i]) for i in range(len(texts))]
+        return {"tokens": texts, "token_logprobs": [num(rec[0]) for rec in recs],
+                "top_logprobs": [{self.token_text(i): num(l) for i, l in zip(rec[1], rec[2])} for rec in recs],
+                "text_offset": offs}
 
     def submit(self, prompt, body: Dict[str, Any], session: Optional[str], stream: bool = False) -> _Request:
         params = self.sampling(body)
@@ -736,15 +834,19 @@ class RoundtableServer:
         a stop id, decoded, cut at a stop string), minus a trailing incomplete UTF-8 character (a
         byte-level BPE token can end mid-character) and minus a tail that may still become a stop
         string: both are held back until the next piece decides."""
-        gen = ids[:params.max_new_tokens]
-        if not params.ignore_eos:
-            gen = cut_at_stop(gen, self.engine.tokenizer.stop_ids)
-        text = self.engine.tokenizer.decode(gen).rstrip("\ufffd")
+        text = self.engine.tokenizer.decode(self.kept_ids(ids, params)).rstrip("\ufffd")
         if stops:
             text, hit = cut_at_stop_strings(text, stops)
             if not hit:
                 text = text[:len(text) - stop_prefix_hold(text, stops)]
         return text
+
+    def kept_ids(self, ids: List[int], params: SamplingParams) -> List[int]:
+        """``ids`` as the final result keeps them: cut at max_new_tokens and at a stop id."""
+        gen = ids[:params.max_new_tokens]
+        if not params.ignore_eos:
+            gen = cut_at_stop(gen, self.engine.tokenizer.stop_ids)
+        return gen
 
     def generate(self, prompt: str, body: Dict[str, Any], session: Optional[str]) -> Tuple[Any, _Request]:
         r = self.submit(prompt, body, session)
