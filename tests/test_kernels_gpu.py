@@ -61,9 +61,20 @@ def test_activations():
 
 
 def make_cache(nb, hkv, d, seed=0):
-    kc = bf(nb, hkv, 32, d, seed=seed)
-    vc = bf(nb, hkv, d, 32, seed=seed + 1)
+    """``nb`` blocks of random K/V plus one more, block ``nb``, for the block tables' padding entries
+    (:func:`poison_padding` fills it once the queries exist)."""
+    kc = bf(nb + 1, hkv, 32, d, seed=seed)
+    vc = bf(nb + 1, hkv, d, 32, seed=seed + 1)
     return kc, vc
+
+
+def poison_padding(kc, vc, q):
+    """The padding block (the last one): K = 8 x the mean query per kv head, V = 96, all finite; a
+    read through a padding entry then moves the output far outside any tolerance."""
+    hkv, d = kc.shape[1], kc.shape[3]
+    qm = 8 * q.float().reshape(-1, hkv, q.shape[-2] // hkv, d).mean((0, 2))
+    ref.k_blocks(kc)[-1] = qm.to(kc.dtype).reshape(hkv, d // 32, 1, 32).expand(hkv, d // 32, 32, 32)
+    vc[-1] = 96.0
 
 
 @pytest.mark.parametrize("hq,hkv,d,rope", [(32, 8, 128, True), (12, 12, 64, False), (8, 1, 128, True)])
@@ -93,13 +104,14 @@ def test_paged_decode(hq, hkv, d, splits):
     kc, vc = make_cache(nb, hkv, d, seed=11)
     perm = torch.randperm(nb).tolist()
     maxb = max((l + 31) // 32 for l in lens)
-    bt = torch.zeros(B, maxb, dtype=torch.int32)
+    bt = torch.full((B, maxb), nb, dtype=torch.int32)         # padding: the poison block
     i = 0
     for b, l in enumerate(lens):
         n = (l + 31) // 32
         bt[b, :n] = torch.tensor(perm[i:i + n], dtype=torch.int32)
         i += n
     q = bf(B, hq, d, seed=12)
+    poison_padding(kc, vc, q)
     cl = torch.tensor(lens, dtype=torch.int32)
     scale = 1 / math.sqrt(d)
     ws = ops.DecodeWorkspace(B, hq, d, splits, DEV)
@@ -149,7 +161,7 @@ def test_paged_decode_shared_prefix_groups(hq, hkv, d, splits, layout):
     kc, vc = make_cache(nb, hkv, d, seed=21)
     perm = torch.randperm(nb, generator=g).tolist()
     maxb = max((l + 31) // 32 for l in lens)
-    bt = torch.zeros(B, maxb, dtype=torch.int32)
+    bt = torch.full((B, maxb), nb, dtype=torch.int32)         # padding: the poison block
     nxt = 0
     b = 0
     for label, sh, ls in spec:
@@ -163,6 +175,7 @@ def test_paged_decode_shared_prefix_groups(hq, hkv, d, splits, layout):
     groups, nmax = ops.decode_groups(group_of, shared, G)
     assert nmax <= max(1, 16 // G)
     q = bf(B, hq, d, seed=22)
+    poison_padding(kc, vc, q)
     cl = torch.tensor(lens, dtype=torch.int32)
     scale = 1 / math.sqrt(d)
     ws = ops.DecodeWorkspace(B, hq, d, splits, DEV, max_group=16 // G)
@@ -186,13 +199,14 @@ def test_paged_decode_long_context(splits):
     kc, vc = make_cache(nb, hkv, d, seed=21)
     perm = torch.randperm(nb, generator=torch.Generator().manual_seed(5)).tolist()
     maxb = max((l + 31) // 32 for l in lens)
-    bt = torch.zeros(B, maxb, dtype=torch.int32)
+    bt = torch.full((B, maxb), nb, dtype=torch.int32)         # padding: the poison block
     i = 0
     for b, l in enumerate(lens):
         n = (l + 31) // 32
         bt[b, :n] = torch.tensor(perm[i:i + n], dtype=torch.int32)
         i += n
     q = bf(B, hq, d, seed=22)
+    poison_padding(kc, vc, q)
     cl = torch.tensor(lens, dtype=torch.int32)
     scale = 1 / math.sqrt(d)
     ws = ops.DecodeWorkspace(B, hq, d, splits, DEV)
@@ -234,7 +248,7 @@ def test_prefill_varlen(hq, hkv, d):
     kc, vc = make_cache(nb, hkv, d, seed=21)
     perm = torch.randperm(nb).tolist()
     maxb = max(nb_each)
-    bt = torch.zeros(S, maxb, dtype=torch.int32)
+    bt = torch.full((S, maxb), nb, dtype=torch.int32)         # padding: the poison block
     i = 0
     for s, n in enumerate(nb_each):
         bt[s, :n] = torch.tensor(perm[i:i + n], dtype=torch.int32)
@@ -245,6 +259,7 @@ def test_prefill_varlen(hq, hkv, d):
     cu_t = torch.tensor(cu, dtype=torch.int32)
     st = torch.tensor([sp for sp, _ in specs], dtype=torch.int32)
     q = bf(cu[-1], hq, d, seed=22)
+    poison_padding(kc, vc, q)
     scale = 1 / math.sqrt(d)
     out = ops.prefill_attention(q, kc, vc, bt.to(DEV), cu_t.to(DEV), st.to(DEV), scale)
     exp = ref.prefill_attention(q.cpu(), kc.cpu(), vc.cpu(), bt, cu_t, st, scale)
@@ -260,7 +275,7 @@ def test_prefill_long_prefix():
     nb = sum(nb_each) + 2
     kc, vc = make_cache(nb, hkv, d, seed=41)
     perm = torch.randperm(nb, generator=torch.Generator().manual_seed(6)).tolist()
-    bt = torch.zeros(S, max(nb_each), dtype=torch.int32)
+    bt = torch.full((S, max(nb_each)), nb, dtype=torch.int32)    # padding: the poison block
     i = 0
     for s, n in enumerate(nb_each):
         bt[s, :n] = torch.tensor(perm[i:i + n], dtype=torch.int32)
@@ -271,6 +286,7 @@ def test_prefill_long_prefix():
     cu_t = torch.tensor(cu, dtype=torch.int32)
     st = torch.tensor([sp for sp, _ in specs], dtype=torch.int32)
     q = bf(cu[-1], hq, d, seed=42)
+    poison_padding(kc, vc, q)
     scale = 1 / math.sqrt(d)
     out = ops.prefill_attention(q, kc, vc, bt.to(DEV), cu_t.to(DEV), st.to(DEV), scale)
     exp = ref.prefill_attention(q.cpu(), kc.cpu(), vc.cpu(), bt, cu_t, st, scale)
@@ -292,7 +308,7 @@ def test_prefill_key_split(hq, hkv, min_chunk):
     nb = sum(nb_each) + 2
     kc, vc = make_cache(nb, hkv, d, seed=51)
     perm = torch.randperm(nb, generator=torch.Generator().manual_seed(7)).tolist()
-    bt = torch.zeros(S, max(nb_each), dtype=torch.int32)
+    bt = torch.full((S, max(nb_each)), nb, dtype=torch.int32)    # padding: the poison block
     i = 0
     for s, n in enumerate(nb_each):
         bt[s, :n] = torch.tensor(perm[i:i + n], dtype=torch.int32)
@@ -303,6 +319,7 @@ def test_prefill_key_split(hq, hkv, min_chunk):
     cu_t = torch.tensor(cu, dtype=torch.int32)
     st = torch.tensor([sp for sp, _ in specs], dtype=torch.int32)
     q = bf(cu[-1], hq, d, seed=52)
+    poison_padding(kc, vc, q)
     scale = 1 / math.sqrt(d)
     rows = ops.native().prefill_rows_per_tile(hq // hkv, d)
     plan = ops.prefill_split_plan(cu_t, rows, st, hkv, num_cus=1 << 20, min_chunk_tiles=min_chunk)

@@ -1,4 +1,5 @@
-"""fp64 oracle of the elementwise kernels (csrc/norm.hip, activation.hip, rope_cache.hip).
+"""fp64 oracle of the elementwise kernels (csrc/norm.hip, activation.hip, rope_cache.hip), the logit
+processors, the logprobs and the attention kernels.
 
 Plain PyTorch on the CPU. Every operation returns the UNROUNDED fp64 result ``e`` and the
 magnitude ``mag`` its tolerance is built from; :func:`assert_within` compares a kernel's bf16
@@ -22,12 +23,31 @@ fp32 error (unit round-off 2^-24) that is far below a bf16 ulp except where term
   far by 1 / rp, and the step's magnitude with it), so 2^-22 * mag bounds their sum with 1.6x margin.
 * logprobs (csrc/logprobs.hip): ``2^-21 * (1 + |l| + |lse|)`` on fp32 values, ids exactly; the
   slack is measured, not derived: 4x the fp32 CPU reference's own worst error (see LOGPROB_SLACK).
+* attention (csrc/attn_core.h, attention_decode.hip, attention_prefill32.hip, attention_prefill.hip):
+  ``bf16_ulp(e) + ((0 if p_exact else 2^-8) + ATTN_SLACK) * A`` with ``A = sum_j w_j |v_j[d]|``, the
+  softmax-weighted mean of |V| in the output's dimension. All three kernels round every p to bf16
+  for the P.V MFMA (``pack2``, round to nearest) and add the UNROUNDED p into the row sum, so only
+  the numerator ``sum_j p_j v_j`` carries the rounding: at most ``u * sum_j p_j |v_j|``, after the
+  division ``u * A``, with u the unit round-off of bf16. bf16 has 8 significant bits, so u = 2^-8:
+  half a spacing, 2^-9 of the binade's lower end, is 2^-8 of a p just above a power of two and
+  2^-9 only of one just below the next. (A first version of this bound took 2^-9. Exact arithmetic
+  refutes it: 31 keys, weights 0.605 / 0.370 on values of opposite sign, A = 0.5208; bf16 P with
+  every other step in fp64 is off by 1.0885e-3 = 1.07 * 2^-9 * A -- the peaky decode case (28, 4,
+  128), row of 31 keys, head 9, dim 47.) The denominator carries no rounding and storing the result
+  costs one bf16 rounding, ``bf16_ulp(e)``. The 32x32 prefill kernel's deferred rescale
+  (RESCALE_LOG2 = 8) lets p reach 2^8 times the running-max term; the rounding stays relative.
+  ``p_exact`` holds for the census inputs only: every live score is exactly 0, so every p is
+  exp2(0) = 1 under any running max, split or merge, and the row sums are exact integers. The rest
+  (fp32 scores, exp2, fp32 sums, merges) is ATTN_SLACK, measured like LOGPROB_SLACK: 4x the fp32
+  CPU reference's own worst ``|o32 - e| / A`` (ATTN_REF_WORST), never against the kernels. Every
+  output element is compared.
 
 The input builders of the CPU emulation test and the GPU test live here too, so both see the
 same bits.
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -549,3 +569,305 @@ def assert_logprobs(tok_lp, top_id, top_lp, oracle, n_top, what: str = "") -> fl
                        logprob_tol(e_lp[rows], l_top[rows], lse[rows][:, None]), what + " top_lp",
                        dtype=torch.float32)
     return max(r1, r2)
+
+
+# ---- attention (csrc/attn_core.h, attention_decode.hip, attention_prefill32.hip, attention_prefill.hip) ----
+# Tolerance of one output element: attn_tol(e, A, p_exact) = bf16_ulp(e) + ((0 if p_exact else 2^-9)
+# + ATTN_SLACK) * A, with A = sum_j w_j |v_j[d]| the softmax-weighted mean of |V| in that dimension
+# (derivation: the module docstring). ATTN_P_ROUND is the unit round-off of bf16, 2^-8: the relative
+# error of rounding one p to nearest. ATTN_SLACK is measured, not derived: the worst |o32 - e| / A of
+# the fp32 CPU REFERENCE (ops/reference.py, its output before the bf16 cast) over every case of the
+# lists below (ATTN_REF_WORST; tests/test_attention_oracle_cpu.py recomputes and prints it), times 4
+# for the device's exp2, its tile order and its merges, rounded up to a power of two. The worst
+# cases are the steep ramps: at 8 log2 units per key the scores reach 2048, where one fp32 rounding
+# of a score moves the runner-up's weight by 1e-4 of itself, and A is small where the dominant key's
+# value is. It is not tuned against the kernels.
+ATTN_P_ROUND = 2.0 ** -8
+ATTN_REF_WORST = 1.12e-4         # measured (tests/test_attention_oracle_cpu.py::test_reference_worst_is_recorded
+#                                  prints it: 1.115e-4 at the key-split prefill case (32, 8, 128), ramp_r8)
+ATTN_SLACK = 2.0 ** -11          # 4 * 1.12e-4 = 4.48e-4 <= 2^-11 = 4.88e-4
+ATTN_BS = 32
+ATTN_POISON_V = 96.0
+
+ATTN_KINDS = ("random", "peaky", "census", "ramp_r025", "ramp_r8", "ramp_f025", "ramp_f8", "ramp_r006", "onehot")
+ATTN_RAMP = {"ramp_r025": (0.25, False), "ramp_r8": (8.0, False), "ramp_f025": (0.25, True), "ramp_f8": (8.0, True),
+             "ramp_r006": (0.0625, False)}
+ATTN_RAMP_KEYS = 256
+
+ATTN_DECODE_CFGS = ((32, 8, 128), (8, 1, 128), (16, 1, 128), (28, 4, 128), (12, 12, 64), (14, 2, 64))
+ATTN_DECODE_SPLITS = (1, 3, 8, 64)
+ATTN_DECODE_LENS = (1, 31, 32, 33, 64, 65, 257, 1500)
+ATTN_REFILL_CFGS = ((8, 1, 128), (32, 8, 128))
+ATTN_REFILL_LENS = (16417, 40)
+ATTN_REFILL_SPLITS = (1, 2)
+ATTN_REFILL_KINDS = ("census", "onehot")
+ATTN_GROUP_CFGS = ((32, 8, 128), (8, 1, 128), (28, 4, 128), (12, 12, 64))
+ATTN_GROUP_SPLITS = (1, 3, 8, 10, 64)
+# (group label or None, shared blocks, context lengths): a 3-member table with 5 shared blocks and
+# tails of 1 / 33 / 300 keys (at G = 8: wider than 16 columns, cut into sub-groups), a lone row
+# between two groups, 4 members over 3 shared blocks (at G = 4 a full 16-column group) one of which
+# has no private tile, a group with 0 shared blocks, and 2 members over 60 shared blocks
+ATTN_GROUP_LAYOUT = (("A", 5, (161, 193, 460)), (None, 0, (77,)), ("B", 3, (96, 101, 160, 136)),
+                     ("C", 0, (40, 70)), ("D", 60, (1927, 2420)))
+ATTN_PREFILL_CFGS = ((32, 8, 128), (28, 4, 128), (12, 4, 128), (16, 1, 128), (12, 12, 64), (14, 2, 64))
+ATTN_PREFILL_SPECS = ((0, 1), (0, 33), (0, 64), (0, 65), (31, 33), (63, 2), (64, 64), (127, 70), (128, 1), (500, 17),
+                      (0, 257))
+ATTN_SPLIT_CFGS = ((4, 1, 128), (8, 2, 128), (28, 4, 128), (32, 8, 128))
+ATTN_SPLIT_SPECS = ((2345, 129), (0, 257), (31, 1), (9000, 300))
+ATTN_SPLIT_MIN_CHUNK = (1, 3)
+
+
+class AttnCase:
+    """One attention test input, CPU tensors: ``q`` [rows, Hq, D] bf16, the paged ``k_cache`` /
+    ``v_cache``, ``block_tables`` [S, max_blocks] int32 (padding entries: ``poison_block``),
+    ``specs`` = (start, new) per sequence, ``ctx_lens`` / ``cu_q`` / ``start_pos`` int32,
+    ``group_of`` / ``shared`` per sequence (:func:`ops.decode_groups` operands), ``scale``,
+    ``p_exact``."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _attn_rows64(qs, k, v, pos, scale):
+    """fp64 attention of rows ``qs`` [R, Hq, D] over keys ``k`` / ``v`` [n, Hkv, D]; row i sees the
+    keys 0..pos[i]. -> (e, A) [R, Hq, D]."""
+    R, Hq, D = qs.shape
+    n, Hkv, _ = k.shape
+    G = Hq // Hkv
+    e = torch.empty(R, Hq, D, dtype=torch.float64)
+    A = torch.empty_like(e)
+    hidden = torch.arange(n)[None, :] > pos[:, None]                      # [R, n]
+    for h in range(Hkv):
+        qh = qs[:, h * G:(h + 1) * G].double()
+        s = torch.matmul(qh, k[:, h].double().t()) * scale                 # [R, G, n]
+        s.masked_fill_(hidden[:, None, :], float("-inf"))
+        w = torch.softmax(s, dim=-1)
+        vh = v[:, h].double()
+        e[:, h * G:(h + 1) * G] = torch.matmul(w, vh)
+        A[:, h * G:(h + 1) * G] = torch.matmul(w, vh.abs())
+    return e, A
+
+
+def _attn_gather(k_cache, v_cache, bt_row, n):
+    """Keys / values 0..n-1 of one block-table row, as ops/reference.py gathers them: K through
+    ``k_rows`` (chunk-major blocks), V from the transposed ``[block, head, D, 32]`` layout."""
+    from .reference import k_rows
+    bs = k_cache.shape[2]
+    nblk = (n + bs - 1) // bs
+    blocks = bt_row[:nblk].long()
+    k = k_rows(k_cache, blocks)[:n]
+    v = v_cache[blocks].permute(0, 3, 1, 2).reshape(nblk * bs, v_cache.shape[1], -1)[:n]
+    return k, v
+
+
+def paged_attention_decode64(q, k_cache, v_cache, block_tables, ctx_lens, scale):
+    """fp64 twin of ops.paged_attention_decode: ``(e, A)`` [B, Hq, D], unrounded."""
+    B = q.shape[0]
+    e = torch.empty(q.shape, dtype=torch.float64)
+    A = torch.empty_like(e)
+    for b in range(B):
+        n = int(ctx_lens[b])
+        k, v = _attn_gather(k_cache, v_cache, block_tables[b], n)
+        e[b:b + 1], A[b:b + 1] = _attn_rows64(q[b:b + 1], k, v, torch.tensor([n - 1]), scale)
+    return e, A
+
+
+def prefill_attention64(q, k_cache, v_cache, block_tables, cu_q, start_pos, scale):
+    """fp64 twin of ops.prefill_attention (row i of sequence s sees keys 0..start_pos[s] + i):
+    ``(e, A)`` [T, Hq, D], unrounded."""
+    e = torch.zeros(q.shape, dtype=torch.float64)
+    A = torch.zeros_like(e)
+    for s in range(cu_q.shape[0] - 1):
+        a, b = int(cu_q[s]), int(cu_q[s + 1])
+        if b == a:
+            continue
+        st = int(start_pos[s])
+        k, v = _attn_gather(k_cache, v_cache, block_tables[s], st + b - a)
+        e[a:b], A[a:b] = _attn_rows64(q[a:b], k, v, torch.arange(st, st + b - a), scale)
+    return e, A
+
+
+def attn_tol(e, A, p_exact: bool = False):
+    return bf16_ulp(e) + ((0.0 if p_exact else ATTN_P_ROUND) + ATTN_SLACK) * A.double()
+
+
+def error_ratio(got, e, tol) -> float:
+    """Worst ``|got - e| / tol`` (no assertion; 0 / 0 counts as 0): how far a deliberately wrong
+    result lies outside a tolerance."""
+    d = (got.detach().cpu().double().reshape(-1) - e.double().reshape(-1)).abs()
+    t = tol.double().reshape(-1)
+    r = torch.where(d > 0, d / t, torch.zeros_like(d))
+    r = torch.where(torch.isfinite(d), r, torch.full_like(d, float("inf")))     # NaN / inf: outside
+    return float(r.max()) if r.numel() else 0.0
+
+
+def attn_marks(L: int, lo: int = 0) -> List[int]:
+    """The boundary keys of a row of ``L`` keys (wrapped into the row when it is short), those at
+    or past ``lo``: 0, 7, 8, 31, 32, L-33, L-32, L-2, L-1, L/2, and the last key of tile 510 and the
+    first and last keys of tiles 511 and 512 (the plan row's limit) where the row has them."""
+    cand = [0, 7, 8, 31, 32, L - 33, L - 32, L - 2, L - 1, L // 2]
+    cand += [j for j in (511 * 32 - 1, 511 * 32, 512 * 32 - 1, 512 * 32, 513 * 32 - 1) if j < L]
+    out: List[int] = []
+    for c in cand:
+        c %= L
+        if c >= lo and c not in out:
+            out.append(c)
+    return out
+
+
+def _attn_seq(kind, qs, st, new, hkv, d, scale, u, g, lo):
+    """Logical K, V [L, hkv, d] (float, bf16-exact) of one sequence for rows ``qs`` [new, hq, d]
+    (float) at positions st..st+new-1; ``lo``: first key this sequence owns (shared members)."""
+    L = st + new
+    hq = qs.shape[1]
+    G = hq // hkv
+    K = torch.randn(L, hkv, d, generator=g)
+    V = torch.randn(L, hkv, d, generator=g)
+    if kind == "census":
+        K.zero_()
+        V.zero_()
+        marks = attn_marks(L)
+        for i in range(d // 2):
+            V[marks[i % len(marks)], :, i] = 1.0
+        j = torch.arange(L)
+        V[j, :, d // 2 + (j // ATTN_BS) % (d // 2)] = 1.0
+    elif kind in ATTN_RAMP:
+        gap, falling = ATTN_RAMP[kind]
+        # scores rise (fall) by about ``gap`` log2 units per key: q . u = 8 d, c a power of two
+        c = 2.0 ** round(math.log2(gap / (8.0 * d * scale * math.log2(math.e))))
+        n = min(L, ATTN_RAMP_KEYS)
+        r = torch.zeros(L)
+        if falling:
+            r[:n] = torch.arange(n, 0, -1, dtype=torch.float32)
+        else:
+            r[L - n:] = torch.arange(1, n + 1, dtype=torch.float32)
+        K = (r * c)[:, None, None] * u[None]
+    elif kind == "onehot":
+        K *= 0.05
+        marks = attn_marks(L, lo)
+        qm = qs.reshape(new, hkv, G, d).mean(2)                             # [new, hkv, d]
+        if new == 1:        # decode: one key per (row, kv head)
+            for h in range(hkv):
+                if marks:
+                    K[marks[(st + h) % len(marks)], h] = 4.0 * qm[0, h]
+        else:               # prefill: the boundary keys, each aligned with the first row that sees it
+            for i, mk in enumerate(marks):
+                K[mk] = 4.0 * qm[mk - st if mk >= st else i % new]
+    return K.to(torch.bfloat16).float(), V.to(torch.bfloat16).float()
+
+
+def attn_case(kind: str, hq: int, hkv: int, d: int, specs, layout=None, seed: int = 0) -> AttnCase:
+    """One attention input of ``kind`` (ATTN_KINDS) for sequences ``specs`` = (start, new) (decode:
+    (ctx - 1, 1)), ``layout`` = (label, shared blocks) per sequence for shared-prefix groups.
+
+    random: N(0,1) q, K, V. peaky: q x 6 (largest weight 0.7..0.99). census: K = 0, V = 0/1 markers
+    (dims < D/2 one boundary key each, :func:`attn_marks`; dims >= D/2 the tile classes
+    ``(j // 32) % (D/2)``): outputs are counts / L, p_exact. ramp_*: K = r_j c u over 256 positions
+    (rising: the last, falling: the first), 0 elsewhere, r_j integers and c a power of two so K is
+    exact; q = 8 u + 0.25 noise; nominal gap 0.0625 / 0.25 / 8 log2 units per key. onehot: one key
+    per (row, kv head) at a boundary position aligned with the group's mean query x 4, other K x 0.05.
+
+    Poison, every kind: K = 8 x (mean query of the rows that could reach the slot) per kv head,
+    V = 96, in every slot of a row's last block at or past its end, in every block no row references
+    and in one dedicated block every block-table padding entry points to. All finite."""
+    from .reference import write_k
+    bs = ATTN_BS
+    S = len(specs)
+    g = _gen(5000 + 97 * ATTN_KINDS.index(kind) + 13 * hq + 7 * hkv + d + 31 * sum(a + 3 * b for a, b in specs)
+             + 1009 * seed)
+    G = hq // hkv
+    scale = 1.0 / math.sqrt(d)
+    u = torch.where(torch.rand(hkv, d, generator=g) < 0.5, -1.0, 1.0)
+    layout = [(None, 0)] * S if layout is None else list(layout)
+    qs_all, kv_all, first = [], [], {}
+    for s, (st, new) in enumerate(specs):
+        label, sh = layout[s]
+        member0 = first.setdefault(label, s) if label is not None and sh > 0 else s
+        qs = torch.randn(new, hq, d, generator=g)
+        if kind == "peaky":
+            qs = qs * 6.0
+        elif kind in ATTN_RAMP:
+            qs = 8.0 * u.repeat_interleave(G, 0)[None] + 0.25 * qs
+        qs = qs.to(torch.bfloat16).float()
+        own = sh * bs if member0 != s else 0
+        K, V = _attn_seq(kind, qs, st, new, hkv, d, scale, u, g, own)
+        if own:
+            K[:own], V[:own] = kv_all[member0][0][:own], kv_all[member0][1][:own]
+        qs_all.append(qs)
+        kv_all.append((K, V))
+    # physical placement: shared blocks once per group, then each row's own; + the dedicated poison
+    # block + 3 blocks nobody references, ids shuffled
+    nblk = [(st + new + bs - 1) // bs for st, new in specs]
+    need = sum(nblk[s] - (layout[s][1] if first.get(layout[s][0], s) != s else 0) for s in range(S))
+    nb = need + 4
+    perm = torch.randperm(nb, generator=g).tolist()
+    poison_block = perm.pop()
+    maxb = max(nblk) + 2
+    bt = torch.full((S, maxb), poison_block, dtype=torch.int32)
+    for s in range(S):
+        label, sh = layout[s]
+        m0 = first.get(label, s) if label is not None and sh > 0 else s
+        keep = sh if m0 != s else 0
+        bt[s, :keep] = bt[m0, :keep]
+        bt[s, keep:nblk[s]] = torch.tensor([perm.pop() for _ in range(nblk[s] - keep)], dtype=torch.int32)
+    q = torch.cat(qs_all).to(torch.bfloat16)
+    qmean = lambda t: t.reshape(-1, hkv, G, d).mean((0, 2))                   # noqa: E731  [hkv, d]
+    k_cache = torch.empty(nb, hkv, bs, d, dtype=torch.bfloat16)
+    v_cache = torch.full((nb, hkv, d, bs), ATTN_POISON_V, dtype=torch.bfloat16)
+    allb, off = torch.arange(nb).repeat_interleave(bs), torch.arange(bs).repeat(nb)
+    write_k(k_cache, allb, off, (8.0 * qmean(q.float()))[None].expand(nb * bs, hkv, d))
+    for s, (st, new) in enumerate(specs):
+        L = st + new
+        pos = torch.arange(nblk[s] * bs)
+        blk = bt[s, pos // bs].long()
+        K = torch.cat([kv_all[s][0], (8.0 * qmean(qs_all[s]))[None].expand(nblk[s] * bs - L, hkv, d)])
+        V = torch.cat([kv_all[s][1], torch.full((nblk[s] * bs - L, hkv, d), ATTN_POISON_V)])
+        write_k(k_cache, blk, pos % bs, K)
+        v_cache[blk, :, :, pos % bs] = V.to(torch.bfloat16)
+    cu = [0]
+    for _, new in specs:
+        cu.append(cu[-1] + new)
+    return AttnCase(kind=kind, hq=hq, hkv=hkv, d=d, specs=tuple(specs), q=q, k_cache=k_cache, v_cache=v_cache,
+                    block_tables=bt, poison_block=poison_block, scale=scale, p_exact=kind == "census",
+                    ctx_lens=torch.tensor([a + b for a, b in specs], dtype=torch.int32),
+                    cu_q=torch.tensor(cu, dtype=torch.int32),
+                    start_pos=torch.tensor([a for a, _ in specs], dtype=torch.int32),
+                    group_of=[lb for lb, _ in layout], shared=[sh for _, sh in layout])
+
+
+def attn_decode_case(kind, hq, hkv, d, lens=ATTN_DECODE_LENS) -> AttnCase:
+    return attn_case(kind, hq, hkv, d, [(l - 1, 1) for l in lens])
+
+
+def attn_group_case(kind, hq, hkv, d) -> AttnCase:
+    specs, layout = [], []
+    for label, sh, lens in ATTN_GROUP_LAYOUT:
+        for l in lens:
+            specs.append((l - 1, 1))
+            layout.append((label, sh))
+    return attn_case(kind, hq, hkv, d, specs, layout)
+
+
+def attn_table3_case(kind, hq, hkv, d) -> AttnCase:
+    """The 3-member table of ATTN_GROUP_LAYOUT alone."""
+    label, sh, lens = ATTN_GROUP_LAYOUT[0]
+    return attn_case(kind, hq, hkv, d, [(l - 1, 1) for l in lens], [(label, sh)] * len(lens))
+
+
+def attn_oracle(case: AttnCase, prefill: bool = False):
+    """-> (e, A, tol) of ``case``."""
+    if prefill:
+        e, A = prefill_attention64(case.q, case.k_cache, case.v_cache, case.block_tables, case.cu_q, case.start_pos,
+                                   case.scale)
+    else:
+        e, A = paged_attention_decode64(case.q, case.k_cache, case.v_cache, case.block_tables, case.ctx_lens,
+                                        case.scale)
+    return e, A, attn_tol(e, A, case.p_exact)
+
+
+def attn_prefill_rows(G: int, d: int) -> int:
+    """Query rows of one prefill work tile (csrc/attention_prefill.hip prefill_rows_per_tile; the GPU
+    test holds the two together): the 32x32 kernel for D = 128 and G <= 8, else the 16x16 one."""
+    if d == 128 and G <= 8:
+        return 32 * 8 // (1 if G == 1 else 2 if G == 2 else 4 if G <= 4 else 8)
+    return 16 if G >= 4 else 16 * (4 // G)
