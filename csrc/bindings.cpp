@@ -8,6 +8,7 @@
 
 #include <vector>
 
+#include "grammar_plan.h"
 #include "logprobs_plan.h"
 
 void launch_norm(void* out, const void* x, void* res, const void* w, const void* b, int rows, int H, float eps,
@@ -72,6 +73,11 @@ int launch_token_logprobs(const void* logits, int dtype, int B, int V, int64_t l
                           int64_t ws_words, const int64_t* ids, const int64_t* out, const int64_t* step,
                           int max_steps, int out_ld, float* tok_lp, int* top_id, float* top_lp, int rec_steps,
                           int rec_ld, int rec_cols, hipStream_t stream);
+int launch_grammar_mask(void* logits, int dtype, int B, int V, int64_t ld, const int* meta, const uint8_t* cls,
+                        const uint16_t* tab, int tab_entries, const uint8_t* accept, int state_cap, int n_classes_cap,
+                        int byte_cap, const int* stops, int* state, int rows, const int* tok_off, int64_t n_off,
+                        const uint8_t* tok_bytes, int64_t n_bytes, const int64_t* out, const int64_t* step,
+                        int max_steps, int out_ld, hipStream_t stream);
 int oneshot_create(int world, int rank, int cap_elems, char* handles);
 int oneshot_open(int id, const char* all_handles);
 int oneshot_capacity(int id);
@@ -777,6 +783,55 @@ void token_logprobs(torch::Tensor logits, torch::Tensor n_top, torch::Tensor ws,
 }
 int64_t logprobs_workspace_floats(int64_t B) { return lpr::workspace_words((int)B); }
 
+// Grammar mask (csrc/grammar_mask.hip): -inf over the tokens each row's grammar cannot accept next, in place
+// on logits [B, V] (row stride >= V), from the row's state in slot 0 or, with the graph's out [steps, B] and
+// device step, from slot (*step - 1) & 1 advanced over out[*step - 1, b] (stored to slot *step & 1); capturable.
+void grammar_mask(torch::Tensor logits, torch::Tensor meta, torch::Tensor cls, torch::Tensor tab, torch::Tensor accept,
+                  torch::Tensor stops, torch::Tensor state, torch::Tensor tok_off, torch::Tensor tok_bytes,
+                  c10::optional<torch::Tensor> out, c10::optional<torch::Tensor> step) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1, "grammar_mask: logits must be [B, V] rows");
+  const auto st = logits.scalar_type();
+  TORCH_CHECK(st == torch::kBFloat16 || st == torch::kFloat32, "grammar_mask: logits must be bfloat16 or float32");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  const int64_t ld = B > 1 ? logits.stride(0) : V;
+  TORCH_CHECK(ld >= V && V < (int64_t(1) << 31), "grammar_mask: row stride must be >= V");
+  check_type(meta, torch::kInt32, "meta");
+  check_type(cls, torch::kUInt8, "cls");
+  check_type(tab, torch::kInt16, "tab");
+  check_type(accept, torch::kUInt8, "accept");
+  check_type(stops, torch::kInt32, "stops");
+  check_type(state, torch::kInt32, "state");
+  check_type(tok_off, torch::kInt32, "tok_off");
+  check_type(tok_bytes, torch::kUInt8, "tok_bytes");
+  const int64_t rows = meta.size(0);
+  TORCH_CHECK(meta.dim() == 2 && meta.size(1) == gr::META && cls.dim() == 2 && cls.size(0) == rows && cls.size(1) == 256 &&
+                  tab.dim() == 2 && tab.size(0) == rows && accept.dim() == 2 && accept.size(0) == rows &&
+                  stops.dim() == 2 && stops.size(0) == rows && stops.size(1) == gr::MAX_STOPS && state.dim() == 3 &&
+                  state.size(0) == 2 && state.size(1) == rows && state.size(2) == gr::STATE,
+              "grammar_mask: per-row operands meta [R, 8], cls [R, 256], tab [R, n], accept [R, s], stops [R, 8], "
+              "state [2, R, 4]");
+  const int64_t* op = nullptr;
+  const int64_t* sp = nullptr;
+  int max_steps = 0, out_ld = 0;
+  if (step.has_value() && step->defined()) {
+    TORCH_CHECK(out.has_value() && out->defined(), "grammar_mask: step needs out");
+    check_type(*out, torch::kInt64, "out");
+    check_type(*step, torch::kInt64, "step");
+    TORCH_CHECK(out->dim() == 2 && out->size(1) >= B && step->numel() >= 1, "grammar_mask: out [steps, B], step [1]");
+    op = out->data_ptr<int64_t>();
+    sp = step->data_ptr<int64_t>();
+    max_steps = (int)out->size(0);
+    out_ld = (int)out->size(1);
+  }
+  const int rc = launch_grammar_mask(
+      logits.data_ptr(), st == torch::kBFloat16 ? 0 : 1, (int)B, (int)V, ld, meta.data_ptr<int>(),
+      cls.data_ptr<uint8_t>(), reinterpret_cast<const uint16_t*>(tab.data_ptr<int16_t>()), (int)tab.size(1),
+      accept.data_ptr<uint8_t>(), (int)accept.size(1), gr::MAX_CLASSES, gr::TOKEN_BYTE_CAP, stops.data_ptr<int>(),
+      state.data_ptr<int>(), (int)rows, tok_off.data_ptr<int>(), tok_off.numel(), tok_bytes.data_ptr<uint8_t>(),
+      tok_bytes.numel(), op, sp, max_steps, out_ld, cur_stream());
+  TORCH_CHECK(rc == 0, "grammar_mask: unsupported configuration (rc=", rc, ")");
+}
+
 void shuffle_weight(torch::Tensor Ws, torch::Tensor W, c10::optional<torch::Tensor> gamma, int64_t rope_heads,
                     int64_t head_dim, bool swiglu) {
   check_bf16(Ws, "Ws");
@@ -979,6 +1034,12 @@ PYBIND11_MODULE(_C, m) {
         py::arg("top_id"), py::arg("top_lp"), py::arg("ids") = py::none(), py::arg("out") = py::none(),
         py::arg("step") = py::none());
   m.def("logprobs_workspace_floats", &logprobs_workspace_floats);
+  m.def("grammar_mask", &grammar_mask, py::arg("logits"), py::arg("meta"), py::arg("cls"), py::arg("tab"),
+        py::arg("accept"), py::arg("stops"), py::arg("state"), py::arg("tok_off"), py::arg("tok_bytes"),
+        py::arg("out") = py::none(), py::arg("step") = py::none());
+  // the grammar limits engine/grammar.py repeats (tests hold the two together)
+  m.attr("GRAMMAR_LIMITS") = std::vector<int>{gr::MAX_DEPTH, gr::MAX_STATES, gr::MAX_CLASSES, gr::MAX_TABLE,
+                                              gr::TOKEN_BYTE_CAP, gr::MAX_STOPS, gr::LDS_ENTRIES};
   m.attr("arch") = "gfx950";
   // the attention limits ops/__init__.py repeats for its CPU path (tests hold the two together)
   m.attr("ATTN_PLAN_HDR") = attn_plan_hdr();

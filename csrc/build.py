@@ -71,7 +71,8 @@ def build(verbose: bool = False, jobs: int = 8) -> str:
     bsrc = os.path.join(HERE, "bindings.cpp")
     bobj = os.path.join(BUILD, "bindings.cpp.o")
     objs.append(bobj)
-    if _newer(bsrc, bobj, [os.path.join(HERE, "logprobs_plan.h")]):     # the one header bindings.cpp includes
+    # the headers bindings.cpp includes
+    if _newer(bsrc, bobj, [os.path.join(HERE, h) for h in ("logprobs_plan.h", "grammar_plan.h", "grammar_core.h")]):
         jobs_list.append([HIPCC, *common, "-I", py_inc, *sum((["-I", i] for i in incs), []),
                           "-DTORCH_EXTENSION_NAME=_C", "-DTORCH_API_INCLUDE_EXTENSION_H", "-c", bsrc, "-o", bobj])
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:

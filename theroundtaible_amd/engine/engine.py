@@ -678,6 +678,7 @@ class Engine:
 
     def _run_turns_ordered(self, turns: Sequence[Turn]) -> List[TurnOutput]:
         t_start = time.perf_counter()
+        self.check_grammars(turns)
         enc = [self.encode_prompt_split(t.prompt) for t in turns]
         targets = [ids for ids, _ in enc]
         self._sync()
@@ -712,7 +713,7 @@ class Engine:
         dev_gen = getattr(self, "_dev_gen", None) or [None] * len(turns)
         gen_lp = self._gen_logprobs
         for b, (t, s, g, n, d, key, nf, dg) in enumerate(zip(turns, seqs, gen, reused, deltas, keys, forced, dev_gen)):
-            text = self.tokenizer.decode(g)
+            text = reply_text(self.tokenizer, g, t.params)
             spre = 0
             if key is not None and key not in seen:     # the group's shared prefill, counted once
                 seen.add(key)
@@ -811,6 +812,7 @@ class Engine:
         """Prefill ``turns`` (LCP reuse, delta only) and sample each first token, WITHOUT decoding:
         returns (sequence, first token, metrics). The first token's K/V is not in the cache yet —
         it is the input of the next :meth:`continue_decode`."""
+        self.check_grammars(turns)
         enc = [self.encode_prompt_split(t.prompt) for t in turns]
         targets = [ids for ids, _ in enc]
         t0 = time.perf_counter()
@@ -884,7 +886,7 @@ class Engine:
         starts = [sq.length if sq.reply_start is None else min(sq.reply_start, sq.length) for sq in seqs]
         runner = self._agreed_graph(len(seqs), max(sq.length for sq in seqs) + steps + 1, groups is not None,
                                     self.dist_greedy(chunk), processors=self.wants_processors(chunk),
-                                    logprobs=self.wants_logprobs(chunk))
+                                    logprobs=self.wants_logprobs(chunk), grammar=self.wants_grammar(chunk))
         with trace.range(f"decode chunk B={len(seqs)} steps={steps}"):
             if runner is not None:
                 toks = runner.run(self, seqs, chunk, first, steps + 1, time.perf_counter() + 1e9, eos, groups,
@@ -917,6 +919,8 @@ class Engine:
         if self.wants_processors(turns):    # the first token obeys bans and penalties too (no reply yet)
             proc = ops.LogitProc(B, dev).fill([(s.tokens, s.length, t.params) for s, t in zip(seqs, turns)])
             ops.apply_logit_processors(logits, proc)
+        if self.wants_grammar(turns):       # the reply's first token is masked from the grammar's start state
+            ops.apply_grammar_mask(logits, self._grammar_mask(B, dev).fill(self.grammar_rows(turns, [[]] * B)))
         first = ops.sample(logits, temp, top_p, top_k, seeds, offs)
         # the first token's logprobs: the processors have run on this tensor, so these are the logits
         # it was sampled from
@@ -931,6 +935,47 @@ class Engine:
     def wants_logprobs(turns: Sequence[Turn]) -> bool:
         """Some row of the batch asks for logprobs."""
         return any(t.params.wants_logprobs() for t in turns)
+
+    @staticmethod
+    def wants_grammar(turns: Sequence[Turn]) -> bool:
+        """Some row of the batch carries a grammar."""
+        return any(t.params.wants_grammar() for t in turns)
+
+    def token_table(self):
+        """The tokenizer's token byte table over this model's logits (engine/grammar.py; cached)."""
+        from .grammar import token_table
+        return token_table(self.tokenizer, int(self.cfg.vocab))
+
+    def _grammar_mask(self, B: int, dev) -> "ops.GrammarMask":
+        """The eager path's mask operands for ``B`` rows, one per (B, device), refilled by every call."""
+        masks = self.__dict__.setdefault("_grammar_masks", {})
+        key = (B, str(dev))
+        if key not in masks:
+            masks[key] = ops.GrammarMask(B, dev, self.token_table())
+        return masks[key]
+
+    def check_grammars(self, turns: Sequence[Turn]) -> None:
+        """ValueError BEFORE any prefill for a turn whose grammar cannot be compiled, is combined with
+        ``ignore_eos`` or cannot be bound to this engine's tokenizer (bound grammars are cached)."""
+        from .grammar import bind
+        for t in turns:
+            if t.params.wants_grammar():
+                t.params.check_grammar()
+                bind(t.params.grammar, self.tokenizer, int(self.cfg.vocab))
+
+    def grammar_rows(self, turns: Sequence[Turn], replies: Sequence[Sequence[int]]) -> list:
+        """Per turn ``(bound grammar, state after the reply tokens so far)``, or None without a grammar:
+        what :meth:`ops.GrammarMask.fill` takes. ValueError for a grammar that cannot be compiled or
+        bound to this engine's tokenizer."""
+        from .grammar import bind
+        rows = []
+        for t, reply in zip(turns, replies):
+            if not t.params.wants_grammar():
+                rows.append(None)
+                continue
+            bound = bind(t.params.grammar, self.tokenizer, int(self.cfg.vocab))
+            rows.append((bound, bound.state_after(reply)))
+        return rows
 
     @staticmethod
     def wants_processors(turns: Sequence[Turn]) -> bool:
@@ -951,7 +996,8 @@ class Engine:
         eos = self.tokenizer.stop_ids
         want_lp = self.wants_logprobs(turns)
         runner = self._agreed_graph(B, max(s.length for s in seqs) + steps, groups is not None, self.dist_greedy(turns),
-                                    processors=self.wants_processors(turns), logprobs=want_lp)
+                                    processors=self.wants_processors(turns), logprobs=want_lp,
+                                    grammar=self.wants_grammar(turns))
         with trace.range(f"decode B={B} steps={steps}"):
             if runner is not None:
                 toks = runner.run(self, seqs, turns, first, steps, deadline, eos, groups)
@@ -1034,6 +1080,13 @@ class Engine:
         # logprobs: the same op as the captured step's last launches, in its ``ids`` form
         lp = ops.LogProbs(B, dev).fill([t.params for t in turns]) if self.wants_logprobs(turns) else None
         self._eager_logprobs = None if lp is None else [None if k < 0 else [] for k in lp.wanted]
+        # grammar: the same op as the captured step; the host advances each row's state token by token
+        gm, gstates, gbound = None, [None] * B, [None] * B
+        if self.wants_grammar(turns):
+            rows = self.grammar_rows(turns, [(s.tokens + o)[r:] for s, o, r in zip(seqs, out, starts)])
+            gm = self._grammar_mask(B, dev).fill(rows)
+            gbound = [None if r is None else r[0] for r in rows]
+            gstates = [None if r is None else r[1] for r in rows]
         for step in range(1, steps):
             pos = list(lens)
             slots = [s.blocks[p // self.kv.block_size] * self.kv.block_size + p % self.kv.block_size
@@ -1047,6 +1100,9 @@ class Engine:
                 logits = logits.contiguous()
                 proc.fill([(s.tokens + o, r, t.params) for s, o, r, t in zip(seqs, out, starts, turns)])
                 ops.apply_logit_processors(logits, proc)
+            if gm is not None:
+                logits = logits.contiguous()
+                ops.apply_grammar_mask(logits, gm.set_states(gstates))
             if dist_greedy:
                 cur = self.tp.greedy_gather(logits, self.cfg.vocab)
             else:
@@ -1059,6 +1115,8 @@ class Engine:
                         acc.append(rec)
             for b, x in enumerate(cur.tolist()):
                 out[b].append(int(x))
+                if gbound[b] is not None:
+                    gstates[b] = gbound[b].advance(gstates[b], int(x))
             lens = [l + 1 for l in lens]
             if step % self.ecfg.sync_every == 0:
                 if self.past_deadline(deadline, step // self.ecfg.sync_every):
@@ -1098,6 +1156,8 @@ class Engine:
             return False
         if self.wants_logprobs(turns):      # so do logprobs
             return False
+        if self.wants_grammar(turns):       # and a grammar row: every rank masks the same full row
+            return False
         return not (self.on_gpu and self.ecfg.use_graphs and self.tp.backend() != "nccl")
 
     def k9_only_step(self) -> bool:
@@ -1107,7 +1167,7 @@ class Engine:
         return os_ is not None and bool(getattr(os_, "gather_ok", False))
 
     def _agreed_graph(self, B: int, max_ctx: int, grouped: bool, dist_greedy: bool, processors: bool = False,
-                      logprobs: bool = False):
+                      logprobs: bool = False, grammar: bool = False):
         """The captured decode step, or None (eager). A capture that fails on ANY rank of a
         tensor-parallel group sends EVERY rank to eager decode: a rank replaying a graph whose K9
         calls no peer issues would wait out each poll bound. The group agrees twice, only when the
@@ -1120,11 +1180,13 @@ class Engine:
         ``processors``: the variant whose step applies the logit processors before K6. It is cached
         beside the plain graph under ``(key, "proc")``; batches without processors never see it.
         ``logprobs``: the variant whose step ends with the logprob launches, under ``(key, "lp")`` or
-        ``(key, "proc", "lp")``; batches without logprobs never see it."""
+        ``(key, "proc", "lp")``; batches without logprobs never see it.
+        ``grammar``: the variant whose step masks the logits by each row's grammar before K6, tag
+        ``"gr"`` after ``"proc"`` and before ``"lp"``; batches without a grammar row never see it."""
         if not (self.on_gpu and self.ecfg.use_graphs):
             return None
         key = self._graph_key(B, grouped, dist_greedy)
-        ckey = self._cache_key(key, processors, logprobs)
+        ckey = self._cache_key(key, processors, logprobs, grammar)
         g = self.graphs.get(ckey)
         if g is not None:
             return g
@@ -1134,7 +1196,8 @@ class Engine:
             with failsafe.stage("capture"):     # the plain graph is constructed exactly as before the flag existed
                 g = DecodeGraph(self, key[0], key[1], grouped=grouped, dist_greedy=dist_greedy, capture=False,
                                 **({"processors": True} if processors else {}),
-                                **({"logprobs": True} if logprobs else {}))
+                                **({"logprobs": True} if logprobs else {}),
+                                **({"grammar": True} if grammar else {}))
         except RuntimeError as e:   # out of memory for the graph's static buffers
             err = e
         failed = self.tp.any_rank(err is not None) if self.tp.size > 1 else err is not None
@@ -1168,20 +1231,20 @@ class Engine:
         return (bucket, ops.decode_splits(bucket, self.model.n_kv_heads, grouped=grouped), grouped, dist_greedy)
 
     @staticmethod
-    def _cache_key(key, processors: bool, logprobs: bool):
-        """The plain key, ``(key, "proc")``, ``(key, "lp")`` or ``(key, "proc", "lp")``."""
-        tags = (("proc",) if processors else ()) + (("lp",) if logprobs else ())
+    def _cache_key(key, processors: bool, logprobs: bool, grammar: bool = False):
+        """The plain key, or the key followed by those of the tags ``"proc"``, ``"gr"``, ``"lp"`` that apply."""
+        tags = (("proc",) if processors else ()) + (("gr",) if grammar else ()) + (("lp",) if logprobs else ())
         return (key, *tags) if tags else key
 
     def _graph_for(self, B: int, max_ctx: int, grouped: bool = False, dist_greedy: bool = False,
-                   processors: bool = False, logprobs: bool = False) -> "DecodeGraph":
+                   processors: bool = False, logprobs: bool = False, grammar: bool = False) -> "DecodeGraph":
         from .graphs import DecodeGraph
         key = self._graph_key(B, grouped, dist_greedy)
-        ckey = self._cache_key(key, processors, logprobs)
+        ckey = self._cache_key(key, processors, logprobs, grammar)
         g = self.graphs.get(ckey)
         if g is None:
             g = DecodeGraph(self, key[0], key[1], grouped=grouped, dist_greedy=dist_greedy, processors=processors,
-                            **({"logprobs": True} if logprobs else {}))
+                            **({"logprobs": True} if logprobs else {}), **({"grammar": True} if grammar else {}))
             self.graphs[ckey] = g
             self.stats["graph_captures"] = self.stats.get("graph_captures", 0) + 1
         return g
@@ -1218,6 +1281,18 @@ def group_order(keys: Sequence[Optional[str]]) -> List[int]:
     for i, k in enumerate(keys):
         first.setdefault(k if k is not None else ("__alone", i), i)
     return sorted(range(len(keys)), key=lambda i: (first[keys[i] if keys[i] is not None else ("__alone", i)], i))
+
+
+def reply_text(tok, ids: Sequence[int], params: SamplingParams) -> str:
+    """The text of a reply's ids. Under a grammar the trailing stop ids (the one that ends the document,
+    and any sampled after it: nothing else can follow) are kept in the ids but are not part of the text
+    (a tokenizer that prints its special tokens would spoil the document); without a grammar the ids
+    decode as they always did."""
+    ids = list(ids)
+    if params.wants_grammar():
+        while ids and ids[-1] in tok.stop_ids:
+            ids.pop()
+    return tok.decode(ids)
 
 
 def cut_at_stop(ids: List[int], stops: frozenset) -> List[int]:

@@ -31,6 +31,24 @@ class SamplingParams:
     # the n most likely alternatives, on the logits as sampled from (after the processors above,
     # before temperature / top-k / top-p). Never changes the sampled ids.
     logprobs: Optional[int] = None
+    # grammar-constrained decoding (engine/grammar.py, csrc/grammar_mask.hip): None = off, or
+    # {"type": "json_object"} | {"type": "json_schema", "schema": {...}} | {"type": "regex", "pattern": "..."}.
+    # Tokens the grammar cannot accept next get -inf after the processors above and before sampling;
+    # the reply ends with a stop id once the grammar accepts (or is cut short by max_new_tokens).
+    grammar: Optional[dict] = None
+
+    def wants_grammar(self) -> bool:
+        return self.grammar is not None
+
+    def check_grammar(self) -> None:
+        """ValueError for a spec the compiler refuses and for ``ignore_eos`` with a grammar: a
+        constrained reply ends with a stop id (serve.py answers 400)."""
+        if self.grammar is None:
+            return
+        from .grammar import compile_grammar
+        compile_grammar(self.grammar)
+        if self.ignore_eos:
+            raise ValueError("ignore_eos cannot be combined with a grammar: a constrained reply ends with a stop id")
 
     def wants_logprobs(self) -> bool:
         return self.logprobs is not None

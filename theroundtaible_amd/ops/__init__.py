@@ -766,3 +766,102 @@ def token_logprobs(logits: torch.Tensor, lp: LogProbs, ids: Optional[torch.Tenso
         native().token_logprobs(logits, lp.n_top, lp.ws, lp.tok_lp, lp.top_id, lp.top_lp, ids, out, step)
         return lp
     return ref.token_logprobs(logits, lp, ids, out, step)
+
+
+GRAMMAR_MAX_TABLE = ref.GRAMMAR_MAX_TABLE        # table entries a row's slot holds
+GRAMMAR_MAX_STATES = ref.GRAMMAR_MAX_STATES
+
+
+def _grammar_host_tensors(g):
+    """(cls uint8[256], tab int16[n_states * n_classes], accept uint8[n_states]) of a compiled grammar, cached on it."""
+    t = getattr(g, "_host_tensors", None)
+    if t is None:
+        tab = torch.tensor([e - 65536 if e >= 32768 else e for e in g.trans], dtype=torch.int16)
+        t = g._host_tensors = (torch.tensor(list(g.cls), dtype=torch.uint8), tab,
+                               torch.tensor(list(g.accept), dtype=torch.uint8))
+    return t
+
+
+class GrammarMask:
+    """Static per-row operands of :func:`apply_grammar_mask` for ``batch`` rows over one token table
+    (``engine.grammar.TokenTable``), no row with a grammar until :meth:`fill`: ``meta`` [B, 8] int32
+    (active, n_states, n_classes, the three pop targets, n_stop), ``cls`` [B, 256] uint8, ``tab``
+    [B, 65536] int16 (16-bit entries; a row uses the first n_states * n_classes), ``accept`` [B, 4096]
+    uint8, ``stops`` [B, 8] int32 and the two-slot ``state`` [2, B, 4] int32 (q, depth, stack), plus
+    the table's ``tok_off`` int32 [V + 1] / ``tok_bytes`` uint8. A decode graph owns one and refills it
+    per turn; the captured kernel reads these addresses."""
+
+    def __init__(self, batch: int, device, table):
+        z = lambda *s, dt=torch.int32: torch.zeros(*s, dtype=dt, device=device)      # noqa: E731
+        self.meta, self.cls = z(batch, ref.GRAMMAR_META), z(batch, 256, dt=torch.uint8)
+        self.tab = torch.full((batch, GRAMMAR_MAX_TABLE), -1, dtype=torch.int16, device=device)
+        self.accept = z(batch, GRAMMAR_MAX_STATES, dt=torch.uint8)
+        self.stops = torch.full((batch, ref.GRAMMAR_MAX_STOPS), -1, dtype=torch.int32, device=device)
+        self.state = z(2, batch, 4)
+        self.table = table
+        self.tok_off, self.tok_bytes = table.tensors(device)
+        self.active = False
+
+    @staticmethod
+    def _state_row(st) -> list:
+        q, depth, stack = st
+        return [q, depth, stack - (1 << 32) if stack >= (1 << 31) else stack, 0]
+
+    def fill(self, rows) -> "GrammarMask":
+        """``rows``: per batch row ``(bound, state)`` — an ``engine.grammar.BoundGrammar`` over this
+        mask's token table and the row's CURRENT state ``(q, depth, stack)`` (the start state advanced
+        over the reply tokens the host holds) — or None for a row without a grammar."""
+        B = self.meta.shape[0]
+        meta = torch.zeros(B, ref.GRAMMAR_META, dtype=torch.int32)
+        stops = torch.full((B, ref.GRAMMAR_MAX_STOPS), -1, dtype=torch.int32)
+        state = torch.zeros(2, B, 4, dtype=torch.int32)
+        cls = torch.zeros(B, 256, dtype=torch.uint8)
+        dev = self.meta.device
+        self.active = False
+        for b, row in enumerate(rows):
+            if row is None:
+                continue
+            bound, st = row
+            if bound.table is not self.table:
+                raise ValueError("the grammar is bound to another token table")
+            g = bound.g
+            self.active = True
+            c, tab, acc = _grammar_host_tensors(g)
+            sids = list(bound.table.stop_ids)
+            meta[b] = torch.tensor([1, g.n_states, g.n_classes, *g.pop_target, len(sids), 0], dtype=torch.int32)
+            stops[b, :len(sids)] = torch.tensor(sids, dtype=torch.int32)
+            state[0, b] = torch.tensor(self._state_row(st), dtype=torch.int32)
+            cls[b] = c
+            self.tab[b, :tab.numel()].copy_(tab.to(dev, non_blocking=True))
+            self.accept[b, :acc.numel()].copy_(acc.to(dev, non_blocking=True))
+        for dst, src in ((self.meta, meta), (self.stops, stops), (self.state, state), (self.cls, cls)):
+            dst.copy_(src.to(dev, non_blocking=True))
+        return self
+
+    def set_states(self, states) -> "GrammarMask":
+        """Slot 0 of ``state`` only: per row a state or None (the eager path's per-step update)."""
+        rows = torch.tensor([[0, 0, 0, 0] if st is None else self._state_row(st) for st in states], dtype=torch.int32)
+        self.state[0, :rows.shape[0]].copy_(rows.to(self.state.device, non_blocking=True))
+        return self
+
+    def states(self, slot: int):
+        """Slot ``slot`` on the host: per row ``(q, depth, stack)``."""
+        return [(q, d, s & 0xFFFFFFFF) for q, d, s, _ in self.state[slot].cpu().tolist()]
+
+
+def apply_grammar_mask(logits: torch.Tensor, gm: GrammarMask, out: Optional[torch.Tensor] = None,
+                       step: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """In place on ``logits`` [B, V] (bf16 or fp32, row stride >= V): ``-inf`` over every token the row's
+    grammar cannot accept next (csrc/grammar_mask.hip; semantics: ops/reference.py); allowed
+    elements, rows without a grammar and columns past V are not written. ``step=None``: each row's
+    state is slot 0 of ``gm.state``, as :meth:`GrammarMask.fill` / ``set_states`` left it. With the
+    graph's ``out`` [steps, B] and device ``step`` the call is capturable: at ``step = s > 0`` the state
+    is slot ``(s - 1) & 1`` advanced over the token K6 recorded at ``out[s - 1, b]``, stored to slot
+    ``s & 1``."""
+    if logits.shape[1] > gm.table.vocab:
+        raise ValueError(f"the token table covers {gm.table.vocab} ids, the logits have {logits.shape[1]}")
+    if _use_native(logits):
+        native().grammar_mask(logits, gm.meta, gm.cls, gm.tab, gm.accept, gm.stops, gm.state, gm.tok_off,
+                              gm.tok_bytes, out if step is not None else None, step)
+        return logits
+    return ref.apply_grammar_mask(logits, gm, out if step is not None else None, step)

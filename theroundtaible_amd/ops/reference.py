@@ -538,3 +538,169 @@ def token_logprobs(logits: torch.Tensor, lp, ids=None, out=None, step=None):
         t = int(toks[b])
         lp.tok_lp[rec, b] = (l[t] - lse) if 0 <= t < V else float("nan")
     return lp
+
+
+# ---- grammar mask (csrc/grammar_mask.hip, walk: csrc/grammar_core.h) -------------------------------
+
+GRAMMAR_MAX_DEPTH = 32                # engine/grammar.py holds the same limits (tests hold them together)
+GRAMMAR_MAX_STATES = 4096
+GRAMMAR_MAX_CLASSES = 64
+GRAMMAR_MAX_TABLE = 65536
+GRAMMAR_TOKEN_BYTE_CAP = 128
+GRAMMAR_MAX_STOPS = 8
+GRAMMAR_Q_FIN, GRAMMAR_Q_DEAD = -1, -2
+GRAMMAR_META = 8                      # ints per row: active, n_states, n_classes, pop obj / arr / empty, n_stop, pad
+
+
+class GrammarRow:
+    """Row ``b`` of a GrammarMask's device-format operands, read back to the host."""
+
+    def __init__(self, gm, b: int):
+        m = [int(x) for x in gm.meta[b].tolist()]
+        self.active = m[0] != 0
+        self.ns = min(max(m[1], 0), gm.accept.shape[1])
+        self.nc = min(max(m[2], 0), GRAMMAR_MAX_CLASSES)
+        if self.ns * self.nc > gm.tab.shape[1]:
+            self.ns = 0
+        self.pops = m[3:6]
+        n_stop = min(max(m[6], 0), GRAMMAR_MAX_STOPS)
+        self.stops = [int(x) for x in gm.stops[b, :n_stop].tolist()]
+        self.cls = gm.cls[b].cpu().long()
+        self.tab = gm.tab[b, :self.ns * self.nc].cpu().long() & 0xFFFF
+        self.accept = gm.accept[b].cpu()
+        self.tok_off = gm.tok_off.cpu().long()
+        self.tok_bytes = gm.tok_bytes.cpu()
+
+
+def grammar_walk(row: GrammarRow, st: Tuple[int, int, int], data) -> Tuple[int, int, int]:
+    """grammar_core.h ``walk``: advance (q, depth, stack) over bytes; (Q_DEAD, 0, 0) when it dies."""
+    q, depth, stack = st
+    dead = (GRAMMAR_Q_DEAD, 0, 0)
+    if q < 0:
+        return st
+    if q >= row.ns or not 0 <= depth <= GRAMMAR_MAX_DEPTH:
+        return dead
+    for byte in data:
+        c = int(row.cls[int(byte)])
+        if c >= row.nc:
+            return dead
+        e = int(row.tab[q * row.nc + c])
+        if e == 0xFFFF:
+            return dead
+        act = e & 3
+        if act == 3:
+            if depth == 0:
+                return dead
+            depth -= 1
+            stack &= ~(1 << depth)
+            q = row.pops[2 if depth == 0 else (stack >> (depth - 1)) & 1]
+        else:
+            if act:
+                if depth == GRAMMAR_MAX_DEPTH:
+                    return dead
+                stack |= (act - 1) << depth
+                depth += 1
+            q = e >> 2
+        if not 0 <= q < row.ns:
+            return dead
+    return (q, depth, stack)
+
+
+def grammar_token_bytes(row: GrammarRow, tok: int, V: int) -> bytes:
+    """The bytes of ``tok``; empty for an id outside [0, V), a zero-length token or one over the byte cap."""
+    if not 0 <= tok < V:
+        return b""
+    a, b = int(row.tok_off[tok]), int(row.tok_off[tok + 1])
+    if a < 0 or b <= a or b > row.tok_bytes.numel() or b - a > GRAMMAR_TOKEN_BYTE_CAP:
+        return b""
+    return bytes(row.tok_bytes[a:b].tolist())
+
+
+def grammar_advance(row: GrammarRow, st, tok: int, V: int):
+    """grammar_core.h ``advance``: FIN / DEAD stay, a stop id gives FIN, an unusable token or a dead walk DEAD."""
+    if st[0] < 0:
+        return st
+    if tok in row.stops:
+        return (GRAMMAR_Q_FIN, 0, 0)
+    data = grammar_token_bytes(row, tok, V)
+    return grammar_walk(row, st, data) if data else (GRAMMAR_Q_DEAD, 0, 0)
+
+
+def grammar_allowed(row: GrammarRow, st, V: int) -> torch.Tensor:
+    """bool [V]: the tokens the mask kernel leaves untouched at state ``st`` (every token walked at once,
+    one byte position per iteration)."""
+    q0, d0, s0 = st
+    if q0 >= row.ns or not 0 <= d0 <= GRAMMAR_MAX_DEPTH:
+        q0 = GRAMMAR_Q_DEAD
+    allowed = torch.zeros(V, dtype=torch.bool)
+    if q0 >= 0:
+        lo, hi = row.tok_off[:V], row.tok_off[1:V + 1]
+        lens = hi - lo
+        alive = (lens > 0) & (lens <= GRAMMAR_TOKEN_BYTE_CAP) & (lo >= 0) & (hi <= row.tok_bytes.numel())
+        lens = torch.where(alive, lens, torch.zeros_like(lens))
+        q = torch.full((V,), q0, dtype=torch.int64)
+        depth = torch.full((V,), d0, dtype=torch.int64)
+        stack = torch.full((V,), s0 & 0xFFFFFFFF, dtype=torch.int64)
+        pops = torch.tensor(row.pops, dtype=torch.int64)
+        one = torch.ones(1, dtype=torch.int64)
+        for p in range(int(lens.max()) if V else 0):
+            idx = torch.nonzero(alive & (lens > p)).squeeze(1)
+            if idx.numel() == 0:
+                break
+            c = row.cls[row.tok_bytes[lo[idx] + p].long()]
+            e = row.tab[(q[idx] * row.nc + c).clamp(max=max(row.tab.numel() - 1, 0))] if row.tab.numel() else c * 0 + 0xFFFF
+            dead = (c >= row.nc) | (e == 0xFFFF)
+            act = e & 3
+            pop, push = act == 3, (act == 1) | (act == 2)
+            d, s = depth[idx], stack[idx]
+            dead |= (pop & (d == 0)) | (push & (d == GRAMMAR_MAX_DEPTH))
+            d_pop = (d - 1).clamp(min=0)
+            s_pop = s & ~torch.bitwise_left_shift(one, d_pop)
+            top = torch.where(d_pop == 0, torch.full_like(d, 2), torch.bitwise_right_shift(s_pop, (d_pop - 1).clamp(min=0)) & 1)
+            s_push = s | torch.bitwise_left_shift((act - 1).clamp(min=0), d.clamp(max=GRAMMAR_MAX_DEPTH - 1))
+            qn = torch.where(pop, pops[top], e >> 2)
+            dead |= (qn < 0) | (qn >= row.ns)
+            keep = ~dead
+            alive[idx[dead]] = False
+            ik = idx[keep]
+            q[ik] = qn[keep]
+            depth[ik] = torch.where(pop, d_pop, torch.where(push, d + 1, d))[keep]
+            stack[ik] = torch.where(pop, s_pop, torch.where(push, s_push, s))[keep]
+        allowed = alive
+    stop_ok = q0 < 0 or bool(row.accept[q0])
+    for t in row.stops:
+        if 0 <= t < V:
+            allowed[t] = stop_ok
+    return allowed
+
+
+def grammar_step_state(gm, row: GrammarRow, b: int, V: int, out=None, step=None):
+    """Row b's current state as the kernel derives it, and the slot to store it to (None: no store)."""
+    s = int(step.reshape(-1)[0]) if step is not None and out is not None else 0
+    if s < 0 or s > (out.shape[0] if out is not None else 0):
+        return (GRAMMAR_Q_DEAD, 0, 0), None
+    src = [int(x) for x in gm.state[(s - 1) & 1 if s > 0 else 0, b].tolist()]
+    st = (src[0], src[1], src[2] & 0xFFFFFFFF)
+    if s == 0:
+        return st, None
+    return grammar_advance(row, st, int(out[s - 1, b]), V), s & 1
+
+
+def apply_grammar_mask(logits: torch.Tensor, gm, out=None, step=None) -> torch.Tensor:
+    """Semantics of csrc/grammar_mask.hip (in place): per row with a grammar, -inf over every token that
+    is not allowed at the row's current state; allowed elements, rows without a grammar and columns
+    past V are not written. ``step=None``: the state is slot 0 of ``gm.state``. With the graph's ``out``
+    and ``step = s > 0`` the state is slot ``(s - 1) & 1`` advanced over ``out[s - 1, b]``, stored to slot
+    ``s & 1``."""
+    B, V = logits.shape
+    for b in range(B):
+        if int(gm.meta[b, 0]) == 0:
+            continue
+        row = GrammarRow(gm, b)
+        st, slot = grammar_step_state(gm, row, b, V, out, step)
+        if slot is not None:
+            stack = st[2] - (1 << 32) if st[2] >= (1 << 31) else st[2]
+            gm.state[slot, b] = torch.tensor([st[0], st[1], stack, 0], dtype=torch.int32).to(gm.state.device)
+        allowed = grammar_allowed(row, st, V)
+        logits[b, :V][~allowed.to(logits.device)] = float("-inf")
+    return logits

@@ -47,7 +47,7 @@ from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
 from typing import Any, Dict, List, Optional, Tuple
 
 from .engine import Engine, EngineConfig, SamplingParams, Turn
-from .engine.engine import cut_at_stop
+from .engine.engine import cut_at_stop, reply_text
 from .engine.sampler import MAX_TOP_LOGPROBS
 from .utils import failsafe
 
@@ -237,7 +237,7 @@ class Scheduler:
             if not a.req.params.ignore_eos:
                 gen = cut_at_stop(gen, self.engine.tokenizer.stop_ids)
             m = dict(a.metrics, decode_tokens=len(gen), turn_ms=(time.perf_counter() - a.t0) * 1e3)
-            text = self.engine.tokenizer.decode(gen)
+            text = reply_text(self.engine.tokenizer, gen, r.params)
             if r.stops:
                 text, hit = cut_at_stop_strings(text, r.stops)
                 m["stop_string"] = hit
@@ -687,7 +687,8 @@ class RoundtableServer:
                           # Ollama's names; absent = neutral (Ollama's own 1.1 default is NOT adopted)
                           "repetition_penalty": opts.get("repeat_penalty"), "repeat_last_n": opts.get("repeat_last_n"),
                           "presence_penalty": opts.get("presence_penalty"),
-                          "frequency_penalty": opts.get("frequency_penalty")}
+                          "frequency_penalty": opts.get("frequency_penalty"),
+                          "format": body.get("format")}     # "json" or a schema object (grammar_request)
                 if body.get("stream"):
                     # Ollama's NDJSON stream: one message object per line, then a done record
                     # (a request without "stream" keeps the one-object reply of rounds 1-5)
@@ -761,10 +762,49 @@ class RoundtableServer:
                                 repeat_last_n=num("repeat_last_n", 64, int),
                                 presence_penalty=num("presence_penalty", 0.0, float),
                                 frequency_penalty=num("frequency_penalty", 0.0, float), logit_bias=bias or None,
-                                logprobs=self.logprob_request(body))
+                                logprobs=self.logprob_request(body), grammar=self.grammar_request(body))
         params.check_processors(int(self.engine.cfg.vocab))      # ValueError -> HTTP 400
         params.check_logprobs()
+        params.check_grammar()
+        if params.wants_grammar():      # a tokenizer the grammar cannot be bound to is a 400 too
+            from .engine.grammar import bind
+            bind(params.grammar, self.engine.tokenizer, int(self.engine.cfg.vocab))
         return params
+
+    @staticmethod
+    def grammar_request(body: Dict[str, Any]) -> Optional[Dict[str, Any]]:
+        """The request's grammar (``SamplingParams.grammar``) or None: OpenAI ``response_format``
+        (``{"type": "text"}``, ``{"type": "json_object"}``, ``{"type": "json_schema", "json_schema":
+        {"schema": ...}}``), the extension ``guided_regex`` (a string), or Ollama's ``format``
+        (``"json"`` or a schema object). ValueError (HTTP 400) for a malformed field or two at once."""
+        found = []
+        rf = body.get("response_format")
+        if rf is not None:
+            if not isinstance(rf, dict) or rf.get("type") not in ("text", "json_object", "json_schema"):
+                raise ValueError("'response_format' must be {\"type\": \"text\" | \"json_object\" | \"json_schema\", ...}")
+            if rf["type"] == "json_object":
+                found.append(("response_format", {"type": "json_object"}))
+            elif rf["type"] == "json_schema":
+                js = rf.get("json_schema")
+                if not isinstance(js, dict) or not isinstance(js.get("schema"), dict):
+                    raise ValueError("'response_format.json_schema.schema' must be a schema object")
+                found.append(("response_format", {"type": "json_schema", "schema": js["schema"]}))
+        rx = body.get("guided_regex")
+        if rx is not None:
+            if not isinstance(rx, str):
+                raise ValueError("'guided_regex' must be a string")
+            found.append(("guided_regex", {"type": "regex", "pattern": rx}))
+        fmt = body.get("format")
+        if fmt is not None and fmt != "":
+            if fmt == "json":
+                found.append(("format", {"type": "json_object"}))
+            elif isinstance(fmt, dict):
+                found.append(("format", {"type": "json_schema", "schema": fmt}))
+            else:
+                raise ValueError("'format' must be \"json\" or a JSON schema object")
+        if len(found) > 1:
+            raise ValueError(f"only one of {', '.join(repr(n) for n, _ in found)} may be given")
+        return found[0][1] if found else None
 
     @staticmethod
     def logprob_request(body: Dict[str, Any]) -> Optional[int]:
@@ -834,7 +874,7 @@ class RoundtableServer:
         a stop id, decoded, cut at a stop string), minus a trailing incomplete UTF-8 character (a
         byte-level BPE token can end mid-character) and minus a tail that may still become a stop
         string: both are held back until the next piece decides."""
-        text = self.engine.tokenizer.decode(self.kept_ids(ids, params)).rstrip("\ufffd")
+        text = reply_text(self.engine.tokenizer, self.kept_ids(ids, params), params).rstrip("\ufffd")
         if stops:
             text, hit = cut_at_stop_strings(text, stops)
             if not hit:
