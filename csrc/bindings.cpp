@@ -78,6 +78,13 @@ int launch_grammar_mask(void* logits, int dtype, int B, int V, int64_t ld, const
                         int byte_cap, const int* stops, int* state, int rows, const int* tok_off, int64_t n_off,
                         const uint8_t* tok_bytes, int64_t n_bytes, const int64_t* out, const int64_t* step,
                         int max_steps, int out_ld, hipStream_t stream);
+int launch_grammar_mask_budget(void* logits, int dtype, int B, int V, int64_t ld, const int* meta, const uint8_t* cls,
+                               const uint16_t* tab, int tab_entries, const uint8_t* accept, int state_cap,
+                               int n_classes_cap, int byte_cap, const int* stops, int* state, int rows,
+                               const int* tok_off, int64_t n_off, const uint8_t* tok_bytes, int64_t n_bytes,
+                               const int64_t* out, const int64_t* step, int max_steps, int out_ld, const int* budget,
+                               int budget_rows, const uint16_t* c_acc, const uint16_t* c_pop, int need_states,
+                               const uint8_t* all_live, int flag_states, hipStream_t stream);
 int oneshot_create(int world, int rank, int cap_elems, char* handles);
 int oneshot_open(int id, const char* all_handles);
 int oneshot_capacity(int id);
@@ -786,15 +793,27 @@ int64_t logprobs_workspace_floats(int64_t B) { return lpr::workspace_words((int)
 // Grammar mask (csrc/grammar_mask.hip): -inf over the tokens each row's grammar cannot accept next, in place
 // on logits [B, V] (row stride >= V), from the row's state in slot 0 or, with the graph's out [steps, B] and
 // device step, from slot (*step - 1) & 1 advanced over out[*step - 1, b] (stored to slot *step & 1); capturable.
-void grammar_mask(torch::Tensor logits, torch::Tensor meta, torch::Tensor cls, torch::Tensor tab, torch::Tensor accept,
-                  torch::Tensor stops, torch::Tensor state, torch::Tensor tok_off, torch::Tensor tok_bytes,
-                  c10::optional<torch::Tensor> out, c10::optional<torch::Tensor> step) {
+// What grammar_mask and grammar_mask_budget share: the operand checks and the optional (out, step) pair.
+struct GrammarOperands {
+  int dtype;
+  int64_t B, V, ld, rows;
+  const int64_t* out = nullptr;
+  const int64_t* step = nullptr;
+  int max_steps = 0, out_ld = 0;
+};
+static GrammarOperands grammar_operands(const torch::Tensor& logits, const torch::Tensor& meta, const torch::Tensor& cls,
+                                        const torch::Tensor& tab, const torch::Tensor& accept, const torch::Tensor& stops,
+                                        const torch::Tensor& state, const torch::Tensor& tok_off,
+                                        const torch::Tensor& tok_bytes, const c10::optional<torch::Tensor>& out,
+                                        const c10::optional<torch::Tensor>& step) {
   TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1, "grammar_mask: logits must be [B, V] rows");
   const auto st = logits.scalar_type();
   TORCH_CHECK(st == torch::kBFloat16 || st == torch::kFloat32, "grammar_mask: logits must be bfloat16 or float32");
-  const int64_t B = logits.size(0), V = logits.size(1);
-  const int64_t ld = B > 1 ? logits.stride(0) : V;
-  TORCH_CHECK(ld >= V && V < (int64_t(1) << 31), "grammar_mask: row stride must be >= V");
+  GrammarOperands o;
+  o.dtype = st == torch::kBFloat16 ? 0 : 1;
+  o.B = logits.size(0), o.V = logits.size(1);
+  o.ld = o.B > 1 ? logits.stride(0) : o.V;
+  TORCH_CHECK(o.ld >= o.V && o.V < (int64_t(1) << 31), "grammar_mask: row stride must be >= V");
   check_type(meta, torch::kInt32, "meta");
   check_type(cls, torch::kUInt8, "cls");
   check_type(tab, torch::kInt16, "tab");
@@ -803,33 +822,62 @@ void grammar_mask(torch::Tensor logits, torch::Tensor meta, torch::Tensor cls, t
   check_type(state, torch::kInt32, "state");
   check_type(tok_off, torch::kInt32, "tok_off");
   check_type(tok_bytes, torch::kUInt8, "tok_bytes");
-  const int64_t rows = meta.size(0);
+  const int64_t rows = o.rows = meta.size(0);
   TORCH_CHECK(meta.dim() == 2 && meta.size(1) == gr::META && cls.dim() == 2 && cls.size(0) == rows && cls.size(1) == 256 &&
                   tab.dim() == 2 && tab.size(0) == rows && accept.dim() == 2 && accept.size(0) == rows &&
                   stops.dim() == 2 && stops.size(0) == rows && stops.size(1) == gr::MAX_STOPS && state.dim() == 3 &&
                   state.size(0) == 2 && state.size(1) == rows && state.size(2) == gr::STATE,
               "grammar_mask: per-row operands meta [R, 8], cls [R, 256], tab [R, n], accept [R, s], stops [R, 8], "
               "state [2, R, 4]");
-  const int64_t* op = nullptr;
-  const int64_t* sp = nullptr;
-  int max_steps = 0, out_ld = 0;
   if (step.has_value() && step->defined()) {
     TORCH_CHECK(out.has_value() && out->defined(), "grammar_mask: step needs out");
     check_type(*out, torch::kInt64, "out");
     check_type(*step, torch::kInt64, "step");
-    TORCH_CHECK(out->dim() == 2 && out->size(1) >= B && step->numel() >= 1, "grammar_mask: out [steps, B], step [1]");
-    op = out->data_ptr<int64_t>();
-    sp = step->data_ptr<int64_t>();
-    max_steps = (int)out->size(0);
-    out_ld = (int)out->size(1);
+    TORCH_CHECK(out->dim() == 2 && out->size(1) >= o.B && step->numel() >= 1, "grammar_mask: out [steps, B], step [1]");
+    o.out = out->data_ptr<int64_t>();
+    o.step = step->data_ptr<int64_t>();
+    o.max_steps = (int)out->size(0);
+    o.out_ld = (int)out->size(1);
   }
+  return o;
+}
+
+void grammar_mask(torch::Tensor logits, torch::Tensor meta, torch::Tensor cls, torch::Tensor tab, torch::Tensor accept,
+                  torch::Tensor stops, torch::Tensor state, torch::Tensor tok_off, torch::Tensor tok_bytes,
+                  c10::optional<torch::Tensor> out, c10::optional<torch::Tensor> step) {
+  const GrammarOperands o = grammar_operands(logits, meta, cls, tab, accept, stops, state, tok_off, tok_bytes, out, step);
   const int rc = launch_grammar_mask(
-      logits.data_ptr(), st == torch::kBFloat16 ? 0 : 1, (int)B, (int)V, ld, meta.data_ptr<int>(),
+      logits.data_ptr(), o.dtype, (int)o.B, (int)o.V, o.ld, meta.data_ptr<int>(),
       cls.data_ptr<uint8_t>(), reinterpret_cast<const uint16_t*>(tab.data_ptr<int16_t>()), (int)tab.size(1),
       accept.data_ptr<uint8_t>(), (int)accept.size(1), gr::MAX_CLASSES, gr::TOKEN_BYTE_CAP, stops.data_ptr<int>(),
-      state.data_ptr<int>(), (int)rows, tok_off.data_ptr<int>(), tok_off.numel(), tok_bytes.data_ptr<uint8_t>(),
-      tok_bytes.numel(), op, sp, max_steps, out_ld, cur_stream());
+      state.data_ptr<int>(), (int)o.rows, tok_off.data_ptr<int>(), tok_off.numel(), tok_bytes.data_ptr<uint8_t>(),
+      tok_bytes.numel(), o.out, o.step, o.max_steps, o.out_ld, cur_stream());
   TORCH_CHECK(rc == 0, "grammar_mask: unsupported configuration (rc=", rc, ")");
+}
+
+// Budgeted grammar mask (csrc/grammar_budget.hip): grammar_mask under each row's token budget (budget [R] int32,
+// r = budget - *step), with need [2, R, S] (c_acc, c_pop; 16-bit entries) and the all-live flags [R, S]; meta[:, 7]
+// holds need_cap. Capturable like grammar_mask.
+void grammar_mask_budget(torch::Tensor logits, torch::Tensor meta, torch::Tensor cls, torch::Tensor tab,
+                         torch::Tensor accept, torch::Tensor stops, torch::Tensor state, torch::Tensor tok_off,
+                         torch::Tensor tok_bytes, torch::Tensor budget, torch::Tensor need, torch::Tensor all_live,
+                         c10::optional<torch::Tensor> out, c10::optional<torch::Tensor> step) {
+  const GrammarOperands o = grammar_operands(logits, meta, cls, tab, accept, stops, state, tok_off, tok_bytes, out, step);
+  check_type(budget, torch::kInt32, "budget");
+  check_type(need, torch::kInt16, "need");
+  check_type(all_live, torch::kUInt8, "all_live");
+  TORCH_CHECK(budget.dim() == 1 && need.dim() == 3 && need.size(0) == 2 && need.size(1) == o.rows && all_live.dim() == 2 &&
+                  all_live.size(0) == o.rows,
+              "grammar_mask_budget: budget [R], need [2, R, S], all_live [R, S]");
+  const uint16_t* np = reinterpret_cast<const uint16_t*>(need.data_ptr<int16_t>());     // c_acc = need[0], c_pop = need[1]
+  const int rc = launch_grammar_mask_budget(
+      logits.data_ptr(), o.dtype, (int)o.B, (int)o.V, o.ld, meta.data_ptr<int>(), cls.data_ptr<uint8_t>(),
+      reinterpret_cast<const uint16_t*>(tab.data_ptr<int16_t>()), (int)tab.size(1), accept.data_ptr<uint8_t>(),
+      (int)accept.size(1), gr::MAX_CLASSES, gr::TOKEN_BYTE_CAP, stops.data_ptr<int>(), state.data_ptr<int>(), (int)o.rows,
+      tok_off.data_ptr<int>(), tok_off.numel(), tok_bytes.data_ptr<uint8_t>(), tok_bytes.numel(), o.out, o.step,
+      o.max_steps, o.out_ld, budget.data_ptr<int>(), (int)budget.numel(), np, np + o.rows * need.size(2), (int)need.size(2),
+      all_live.data_ptr<uint8_t>(), (int)all_live.size(1), cur_stream());
+  TORCH_CHECK(rc == 0, "grammar_mask_budget: unsupported configuration (rc=", rc, ")");
 }
 
 void shuffle_weight(torch::Tensor Ws, torch::Tensor W, c10::optional<torch::Tensor> gamma, int64_t rope_heads,
@@ -1037,6 +1085,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("grammar_mask", &grammar_mask, py::arg("logits"), py::arg("meta"), py::arg("cls"), py::arg("tab"),
         py::arg("accept"), py::arg("stops"), py::arg("state"), py::arg("tok_off"), py::arg("tok_bytes"),
         py::arg("out") = py::none(), py::arg("step") = py::none());
+  m.def("grammar_mask_budget", &grammar_mask_budget, py::arg("logits"), py::arg("meta"), py::arg("cls"), py::arg("tab"),
+        py::arg("accept"), py::arg("stops"), py::arg("state"), py::arg("tok_off"), py::arg("tok_bytes"),
+        py::arg("budget"), py::arg("need"), py::arg("all_live"), py::arg("out") = py::none(),
+        py::arg("step") = py::none());
   // the grammar limits engine/grammar.py repeats (tests hold the two together)
   m.attr("GRAMMAR_LIMITS") = std::vector<int>{gr::MAX_DEPTH, gr::MAX_STATES, gr::MAX_CLASSES, gr::MAX_TABLE,
                                               gr::TOKEN_BYTE_CAP, gr::MAX_STOPS, gr::LDS_ENTRIES};

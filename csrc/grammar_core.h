@@ -113,4 +113,60 @@ GR_HD void advance(const Table& t, State& s, const int* stops, int n_stop, const
   walk(t, s, p, n);
 }
 
+// ---- the token budget (engine/grammar.py GrammarBudget states the bound and why the rule is sound) ----
+constexpr uint16_t NEED_INF16 = 0xFFFF;     // a 16-bit entry: no way through single-byte tokens
+constexpr int NEED_INF = 1 << 30;           // need() with such an entry on its way
+constexpr int BUDGET_FREE = 1 << 29;        // a budget that binds nothing
+
+// A row's need arrays: c_acc[q] (to accept, at depth 0) and c_pop[q] (up to and including the next pop),
+// n_states entries each, in global memory or on the host.
+struct Need {
+  const uint16_t* c_acc;
+  const uint16_t* c_pop;
+};
+
+// An upper bound on the tokens that still lead from the live state (q, depth, stack) of table `t` to an
+// accepting one: c_acc[q] at depth 0, else c_pop[q] + one c_pop[pop target] per stack level below the top
+// (two popcounts) + c_acc[pop_empty]. NEED_INF when an entry it reads is NEED_INF16 or an index lies
+// outside the table.
+GR_HD int need(const Table& t, const Need& nd, int q, int depth, uint32_t stack) {
+  if (q < 0 || q >= t.n_states || depth < 0 || depth > MAX_DEPTH) return NEED_INF;
+  if (depth == 0) {
+    const uint16_t a = nd.c_acc[q];
+    return a == NEED_INF16 ? NEED_INF : (int)a;
+  }
+  const uint32_t below = (1u << (depth - 1)) - 1u;     // depth - 1 <= 31
+  int ones = 0;
+  for (uint32_t m = stack & below; m != 0; m &= m - 1) ++ones;
+  const int zeros = depth - 1 - ones;
+  const int on_obj = t.pop_obj, on_arr = t.pop_arr, on_empty = t.pop_empty;
+  if (on_empty < 0 || on_empty >= t.n_states) return NEED_INF;
+  const uint16_t p = nd.c_pop[q], e = nd.c_acc[on_empty];
+  if (p == NEED_INF16 || e == NEED_INF16) return NEED_INF;
+  int total = (int)p + (int)e;
+  if (zeros > 0) {
+    if (on_obj < 0 || on_obj >= t.n_states || nd.c_pop[on_obj] == NEED_INF16) return NEED_INF;
+    total += zeros * (int)nd.c_pop[on_obj];
+  }
+  if (ones > 0) {
+    if (on_arr < 0 || on_arr >= t.n_states || nd.c_pop[on_arr] == NEED_INF16) return NEED_INF;
+    total += ones * (int)nd.c_pop[on_arr];
+  }
+  return total;     // at most 33 * 65534: no overflow
+}
+
+// Tokens the row may still emit, the one sampled now included: the row's budget less the device step.
+GR_HD int remaining(int budget, int64_t step) {
+  const int64_t r = (int64_t)budget - (step > 0 ? step : 0);
+  return r < -1 ? -1 : (r > BUDGET_FREE ? BUDGET_FREE : (int)r);
+}
+
+// THE rule for a non-stop token whose walk stayed live: with r tokens left, one is kept back for the
+// stop id and the document must still fit after this token. (r <= 0: nothing but stop ids.)
+GR_HD bool budget_allows(int need_after, int r) { return r > 0 && need_after <= r - 2; }
+
+// The free-phase shortcut: in a state whose flag says every token with bytes stays live, and with a
+// budget no state's need can bind, the rule allows every token with bytes and no walk is needed.
+GR_HD bool walks_skippable(bool all_live, int need_cap, int r) { return all_live && r > 0 && need_cap <= r - 2; }
+
 }  // namespace gr

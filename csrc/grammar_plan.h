@@ -48,4 +48,18 @@ inline MaskPlan plan_grammar_mask(int B, int V, int64_t ld, int dtype, int tab_e
   return pl;
 }
 
+// The budgeted launch (grammar_budget.hip) takes the same shape and, per row, budget int32, the two need
+// arrays c_acc / c_pop [rows][need_cap_states] of 16-bit entries, the all-live flags [rows][flag_states]
+// and need_cap in meta[7]. Its refusals are the plain launch's, then -12: the need arrays or the flags
+// do not hold a row's state_cap states, or the budget does not cover `rows`.
+inline MaskPlan plan_grammar_budget(int B, int V, int64_t ld, int dtype, int tab_entries, int state_cap, int n_classes_cap,
+                                    int byte_cap, int64_t n_off, int64_t n_bytes, int rows, bool has_out, bool has_step,
+                                    int max_steps, int out_ld, int need_states, int flag_states, int budget_rows) {
+  MaskPlan pl = plan_grammar_mask(B, V, ld, dtype, tab_entries, state_cap, n_classes_cap, byte_cap, n_off, n_bytes, rows,
+                                  has_out, has_step, max_steps, out_ld);
+  if (pl.rc != 0) return pl;
+  if (need_states < state_cap || flag_states < state_cap || budget_rows < rows) return pl.rc = -12, pl.chunks = 0, pl;
+  return pl;
+}
+
 }  // namespace gr

@@ -54,6 +54,9 @@ ENGINE_DEFAULTS: Dict[str, Any] = {
     "presence_penalty": 0.0,
     "frequency_penalty": 0.0,
     "logit_bias": None,
+    # every turn whose reply goes to parse_consensus gets a grammar: free text, then a fenced JSON block that
+    # obeys the consensus schema, always inside max_new_tokens (consensus.consensus_grammar)
+    "consensus_grammar": False,
 }
 
 
@@ -130,7 +133,8 @@ def resolve_weight_quant(value: Optional[str]) -> str:
 
 def engine_settings(config: RoundtableConfig, adapter_id: str) -> Dict[str, Any]:
     """Effective engine settings for one adapter id: defaults <- config.engine <- adapter engine.
-    ``weight_quant`` (engine-wide or per knight) comes back resolved: "none" | "fp8"."""
+    ``weight_quant`` (engine-wide or per knight) comes back resolved: "none" | "fp8".
+    ``consensus_grammar`` (engine-wide or per knight) is a bool; with ``scripted_consensus`` a ConfigError."""
     out = dict(ENGINE_DEFAULTS)
     top = config.raw.get("engine") if isinstance(config.raw, dict) else None
     if isinstance(top, dict):
@@ -143,6 +147,11 @@ def engine_settings(config: RoundtableConfig, adapter_id: str) -> Dict[str, Any]
         out["model"] = resolve_model_name(ac.get("model") if isinstance(ac, dict) else None,
                                           out["default_model"])
     out["weight_quant"] = resolve_weight_quant(out.get("weight_quant"))
+    if not isinstance(out.get("consensus_grammar", False), bool):
+        raise ConfigError(f"{adapter_id}: engine.consensus_grammar must be true or false")
+    if out.get("consensus_grammar") and out.get("scripted_consensus"):
+        raise ConfigError(f"{adapter_id}: engine.consensus_grammar cannot be combined with engine.scripted_consensus",
+                          hint="The script forces the block's tokens; the grammar lets the model write it. Pick one.")
     return out
 
 

@@ -37,6 +37,30 @@ _MEANINGLESS = frozenset({
 })
 
 
+CONSENSUS_OPEN, CONSENSUS_CLOSE = "```json\n", "\n```"
+CONSENSUS_MAX_ITEMS = 6        # agrees_with / pending_issues / files_to_modify; the two request lists take 4
+
+
+def consensus_schema() -> dict:
+    """The consensus block as a JSON schema in the subset ``engine/grammar.py`` compiles: the template's
+    keys in the template's order, ``consensus_score`` one of 0..10, the rest arrays of strings. The
+    strings are unbounded (cheap in automaton states); a token budget closes them."""
+    def strings(n: int) -> dict:
+        return {"type": "array", "items": {"type": "string"}, "maxItems": n}
+
+    return {"type": "object", "properties": {
+        "consensus_score": {"enum": list(range(11))},
+        "agrees_with": strings(CONSENSUS_MAX_ITEMS), "pending_issues": strings(CONSENSUS_MAX_ITEMS),
+        "files_to_modify": strings(CONSENSUS_MAX_ITEMS), "file_requests": strings(4), "verify_commands": strings(4)}}
+
+
+def consensus_grammar() -> dict:
+    """``SamplingParams.grammar`` of a turn whose reply goes to :func:`parse_consensus`: free text, then
+    the fenced block (first pattern of ``_FENCED``) holding an object of :func:`consensus_schema`."""
+    return {"type": "tail", "open": CONSENSUS_OPEN, "body": {"type": "json_schema", "schema": consensus_schema()},
+            "close": CONSENSUS_CLOSE}
+
+
 def _js_truthy(v: Any) -> bool:
     if v is None or v is False:
         return False

@@ -878,7 +878,8 @@ class Engine:
         for sq in seqs:
             self.kv.ensure_capacity(sq, sq.length + steps + 1)
         chunk = [Turn(t.seq_key, t.prompt, SamplingParams(**{**t.params.__dict__, "max_new_tokens": steps + 1,
-                                                              "ignore_eos": True, "stop_on_consensus": False}),
+                                                              "ignore_eos": True, "stop_on_consensus": False,
+                                                              "grammar_budget": t.params.reply_budget()}),
                       t.timeout_s) for t in turns]
         eos = self.tokenizer.stop_ids
         t0 = time.perf_counter()
@@ -886,7 +887,7 @@ class Engine:
         starts = [sq.length if sq.reply_start is None else min(sq.reply_start, sq.length) for sq in seqs]
         runner = self._agreed_graph(len(seqs), max(sq.length for sq in seqs) + steps + 1, groups is not None,
                                     self.dist_greedy(chunk), processors=self.wants_processors(chunk),
-                                    logprobs=self.wants_logprobs(chunk), grammar=self.wants_grammar(chunk))
+                                    logprobs=self.wants_logprobs(chunk), grammar=self.grammar_tag(chunk))
         with trace.range(f"decode chunk B={len(seqs)} steps={steps}"):
             if runner is not None:
                 toks = runner.run(self, seqs, chunk, first, steps + 1, time.perf_counter() + 1e9, eos, groups,
@@ -920,7 +921,9 @@ class Engine:
             proc = ops.LogitProc(B, dev).fill([(s.tokens, s.length, t.params) for s, t in zip(seqs, turns)])
             ops.apply_logit_processors(logits, proc)
         if self.wants_grammar(turns):       # the reply's first token is masked from the grammar's start state
-            ops.apply_grammar_mask(logits, self._grammar_mask(B, dev).fill(self.grammar_rows(turns, [[]] * B)))
+            budgeted = self.grammar_tag(turns) == "grb"      # then with r = max_new_tokens
+            gm = self._grammar_mask(B, dev, budgeted).fill(self.grammar_rows(turns, [[]] * B, budgeted))
+            (ops.apply_grammar_mask_budget if budgeted else ops.apply_grammar_mask)(logits, gm)
         first = ops.sample(logits, temp, top_p, top_k, seeds, offs)
         # the first token's logprobs: the processors have run on this tensor, so these are the logits
         # it was sampled from
@@ -946,27 +949,41 @@ class Engine:
         from .grammar import token_table
         return token_table(self.tokenizer, int(self.cfg.vocab))
 
-    def _grammar_mask(self, B: int, dev) -> "ops.GrammarMask":
-        """The eager path's mask operands for ``B`` rows, one per (B, device), refilled by every call."""
+    @classmethod
+    def grammar_tag(cls, turns: Sequence[Turn]):
+        """False without a grammar row; ``"grb"`` when some row has ``grammar_finish`` or a ``tail`` grammar
+        (the budgeted launch then masks ALL the batch's grammar rows); else ``"gr"``."""
+        if not cls.wants_grammar(turns):
+            return False
+        return "grb" if any(t.params.wants_grammar_budget() for t in turns) else "gr"
+
+    def _grammar_mask(self, B: int, dev, budgeted: bool = False) -> "ops.GrammarMask":
+        """The eager path's mask operands for ``B`` rows, one per (B, device, launch), refilled by every call."""
         masks = self.__dict__.setdefault("_grammar_masks", {})
-        key = (B, str(dev))
+        key = (B, str(dev), budgeted) if budgeted else (B, str(dev))
         if key not in masks:
-            masks[key] = ops.GrammarMask(B, dev, self.token_table())
+            masks[key] = (ops.GrammarBudgetMask if budgeted else ops.GrammarMask)(B, dev, self.token_table())
         return masks[key]
 
     def check_grammars(self, turns: Sequence[Turn]) -> None:
         """ValueError BEFORE any prefill for a turn whose grammar cannot be compiled, is combined with
-        ``ignore_eos`` or cannot be bound to this engine's tokenizer (bound grammars are cached)."""
+        ``ignore_eos`` or cannot be bound to this engine's tokenizer (bound grammars are cached), and for a
+        ``grammar_finish`` turn whose pair cannot finish inside a budget or whose ``max_new_tokens`` is
+        below the grammar's minimum."""
         from .grammar import bind
         for t in turns:
+            t.params.check_grammar()
             if t.params.wants_grammar():
-                t.params.check_grammar()
-                bind(t.params.grammar, self.tokenizer, int(self.cfg.vocab))
+                bound = bind(t.params.grammar, self.tokenizer, int(self.cfg.vocab))
+                if t.params.grammar_finish:
+                    check_budget(bound, t.params.reply_budget())
 
-    def grammar_rows(self, turns: Sequence[Turn], replies: Sequence[Sequence[int]]) -> list:
+    def grammar_rows(self, turns: Sequence[Turn], replies: Sequence[Sequence[int]], budgeted: bool = False) -> list:
         """Per turn ``(bound grammar, state after the reply tokens so far)``, or None without a grammar:
-        what :meth:`ops.GrammarMask.fill` takes. ValueError for a grammar that cannot be compiled or
-        bound to this engine's tokenizer."""
+        what :meth:`ops.GrammarMask.fill` takes. ``budgeted``: a third entry, the tokens the row may
+        still emit (``max_new_tokens`` less the reply so far; None without ``grammar_finish``), for
+        :meth:`ops.GrammarBudgetMask.fill`. ValueError for a grammar that cannot be compiled or bound
+        to this engine's tokenizer."""
         from .grammar import bind
         rows = []
         for t, reply in zip(turns, replies):
@@ -974,7 +991,11 @@ class Engine:
                 rows.append(None)
                 continue
             bound = bind(t.params.grammar, self.tokenizer, int(self.cfg.vocab))
-            rows.append((bound, bound.state_after(reply)))
+            row = (bound, bound.state_after(reply))
+            if budgeted:
+                total = t.params.reply_budget()
+                row += (None if total is None else total - len(reply),)
+            rows.append(row)
         return rows
 
     @staticmethod
@@ -997,7 +1018,7 @@ class Engine:
         want_lp = self.wants_logprobs(turns)
         runner = self._agreed_graph(B, max(s.length for s in seqs) + steps, groups is not None, self.dist_greedy(turns),
                                     processors=self.wants_processors(turns), logprobs=want_lp,
-                                    grammar=self.wants_grammar(turns))
+                                    grammar=self.grammar_tag(turns))
         with trace.range(f"decode B={B} steps={steps}"):
             if runner is not None:
                 toks = runner.run(self, seqs, turns, first, steps, deadline, eos, groups)
@@ -1081,12 +1102,15 @@ class Engine:
         lp = ops.LogProbs(B, dev).fill([t.params for t in turns]) if self.wants_logprobs(turns) else None
         self._eager_logprobs = None if lp is None else [None if k < 0 else [] for k in lp.wanted]
         # grammar: the same op as the captured step; the host advances each row's state token by token
-        gm, gstates, gbound = None, [None] * B, [None] * B
+        gm, gstates, gbound, gleft = None, [None] * B, [None] * B, [None] * B
+        budgeted = self.grammar_tag(turns) == "grb"
         if self.wants_grammar(turns):
-            rows = self.grammar_rows(turns, [(s.tokens + o)[r:] for s, o, r in zip(seqs, out, starts)])
-            gm = self._grammar_mask(B, dev).fill(rows)
+            rows = self.grammar_rows(turns, [(s.tokens + o)[r:] for s, o, r in zip(seqs, out, starts)], budgeted)
+            gm = self._grammar_mask(B, dev, budgeted).fill(rows)
             gbound = [None if r is None else r[0] for r in rows]
             gstates = [None if r is None else r[1] for r in rows]
+            if budgeted:     # tokens each finishing row may still emit; one fewer after every step
+                gleft = [None if r is None else r[2] for r in rows]
         for step in range(1, steps):
             pos = list(lens)
             slots = [s.blocks[p // self.kv.block_size] * self.kv.block_size + p % self.kv.block_size
@@ -1102,7 +1126,11 @@ class Engine:
                 ops.apply_logit_processors(logits, proc)
             if gm is not None:
                 logits = logits.contiguous()
-                ops.apply_grammar_mask(logits, gm.set_states(gstates))
+                if budgeted:
+                    ops.apply_grammar_mask_budget(logits, gm.set_states(gstates).set_budgets(gleft))
+                    gleft = [None if x is None else x - 1 for x in gleft]
+                else:
+                    ops.apply_grammar_mask(logits, gm.set_states(gstates))
             if dist_greedy:
                 cur = self.tp.greedy_gather(logits, self.cfg.vocab)
             else:
@@ -1182,7 +1210,9 @@ class Engine:
         ``logprobs``: the variant whose step ends with the logprob launches, under ``(key, "lp")`` or
         ``(key, "proc", "lp")``; batches without logprobs never see it.
         ``grammar``: the variant whose step masks the logits by each row's grammar before K6, tag
-        ``"gr"`` after ``"proc"`` and before ``"lp"``; batches without a grammar row never see it."""
+        ``"gr"`` after ``"proc"`` and before ``"lp"``; batches without a grammar row never see it.
+        ``grammar="grb"`` (:meth:`grammar_tag`): the step masks with the budgeted launch instead, cached
+        under tag ``"grb"`` in the place of ``"gr"``."""
         if not (self.on_gpu and self.ecfg.use_graphs):
             return None
         key = self._graph_key(B, grouped, dist_greedy)
@@ -1197,7 +1227,7 @@ class Engine:
                 g = DecodeGraph(self, key[0], key[1], grouped=grouped, dist_greedy=dist_greedy, capture=False,
                                 **({"processors": True} if processors else {}),
                                 **({"logprobs": True} if logprobs else {}),
-                                **({"grammar": True} if grammar else {}))
+                                **({"grammar": grammar} if grammar else {}))
         except RuntimeError as e:   # out of memory for the graph's static buffers
             err = e
         failed = self.tp.any_rank(err is not None) if self.tp.size > 1 else err is not None
@@ -1231,9 +1261,11 @@ class Engine:
         return (bucket, ops.decode_splits(bucket, self.model.n_kv_heads, grouped=grouped), grouped, dist_greedy)
 
     @staticmethod
-    def _cache_key(key, processors: bool, logprobs: bool, grammar: bool = False):
-        """The plain key, or the key followed by those of the tags ``"proc"``, ``"gr"``, ``"lp"`` that apply."""
-        tags = (("proc",) if processors else ()) + (("gr",) if grammar else ()) + (("lp",) if logprobs else ())
+    def _cache_key(key, processors: bool, logprobs: bool, grammar=False):
+        """The plain key, or the key followed by those of the tags ``"proc"``, ``"gr"`` (``"grb"`` for the
+        budgeted launch), ``"lp"`` that apply."""
+        gtag = ("grb" if grammar == "grb" else "gr",) if grammar else ()
+        tags = (("proc",) if processors else ()) + gtag + (("lp",) if logprobs else ())
         return (key, *tags) if tags else key
 
     def _graph_for(self, B: int, max_ctx: int, grouped: bool = False, dist_greedy: bool = False,
@@ -1244,7 +1276,7 @@ class Engine:
         g = self.graphs.get(ckey)
         if g is None:
             g = DecodeGraph(self, key[0], key[1], grouped=grouped, dist_greedy=dist_greedy, processors=processors,
-                            **({"logprobs": True} if logprobs else {}), **({"grammar": True} if grammar else {}))
+                            **({"logprobs": True} if logprobs else {}), **({"grammar": grammar} if grammar else {}))
             self.graphs[ckey] = g
             self.stats["graph_captures"] = self.stats.get("graph_captures", 0) + 1
         return g
@@ -1281,6 +1313,15 @@ def group_order(keys: Sequence[Optional[str]]) -> List[int]:
     for i, k in enumerate(keys):
         first.setdefault(k if k is not None else ("__alone", i), i)
     return sorted(range(len(keys)), key=lambda i: (first[keys[i] if keys[i] is not None else ("__alone", i)], i))
+
+
+def check_budget(bound, max_new_tokens: int) -> None:
+    """ValueError when ``grammar_finish`` cannot hold: the pair has a state only multi-byte tokens leave, or
+    ``max_new_tokens`` is below what the shortest document and its stop id take."""
+    need = bound.budget().min_tokens()
+    if max_new_tokens < need:
+        raise ValueError(f"grammar_finish: max_new_tokens={max_new_tokens} is too small for this grammar; the "
+                         f"minimum is {need}")
 
 
 def reply_text(tok, ids: Sequence[int], params: SamplingParams) -> str:

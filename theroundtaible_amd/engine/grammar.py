@@ -16,7 +16,9 @@ Regular grammars (regex, schema) use no actions. The automata work on BYTES: a t
 UTF-8 code point needs no special case, the string states track the sequence.
 
 Front ends: ``{"type": "json_object"}``, ``{"type": "regex", "pattern": ...}``,
-``{"type": "json_schema", "schema": ...}`` (see :func:`compile_grammar`). Whitespace between JSON
+``{"type": "json_schema", "schema": ...}`` and ``{"type": "tail", "open": ..., "body": <schema or regex
+spec>, "close": ...}``: free bytes up to the first ``open``, then the body, then ``close`` (see
+:func:`compile_grammar`). Whitespace between JSON
 tokens is unbounded in all of them: a model may pad, and ``max_new_tokens`` bounds it.
 
 Regex subset (anchored at both ends): literals and escapes (``\\n \\t \\r \\f \\v \\0 \\xHH \\uHHHH``
@@ -45,6 +47,10 @@ DEAD_ENTRY = 0xFFFF
 ACT_NONE, ACT_PUSH0, ACT_PUSH1, ACT_POP = 0, 1, 2, 3
 _DFA_BLOWUP = 8 * GRAMMAR_MAX_STATES     # subset construction gives up here (before minimisation)
 _BOUND_CACHE = 256                       # bound grammars kept per token table, like compiled ones
+TAIL_MAX_BYTES = 32               # a tail grammar's opener and closer
+NEED_INF16 = 0xFFFF               # a 16-bit need entry: no path through single-byte tokens
+NEED_INF = 1 << 30                # need() of a state with such an entry on its way
+BUDGET_FREE = 1 << 29             # a row's budget when nothing bounds it (grammar_finish off)
 
 State = Tuple[int, int, int]      # (q, depth, stack)
 DEAD: State = (Q_DEAD, 0, 0)
@@ -534,7 +540,10 @@ def parse_regex(pattern: str):
     return _RegexParser(pattern).parse()
 
 
-def _ast_to_grammar(kind: str, key: str, ast) -> CompiledGrammar:
+def _ast_to_grammar(kind: str, key: str, ast, opener: bytes = b"") -> CompiledGrammar:
+    """``opener``: the language becomes any bytes up to and including the FIRST occurrence of ``opener``,
+    then ``L(ast)`` (the ``tail`` grammar): the opener's KMP prefix automaton, total on all 256 bytes,
+    stands in front of the NFA, and the subset construction takes tokens across the seam."""
     eps: List[List[int]] = []
     edges: List[List[Tuple[int, int]]] = []      # (byte mask, target)
 
@@ -590,6 +599,26 @@ def _ast_to_grammar(kind: str, key: str, ast) -> CompiledGrammar:
         return a, b
 
     n_start, n_end = build(ast)
+    if opener:
+        m = len(opener)
+        fail = [0] * (m + 1)          # fail[i]: the longest proper border of opener[:i]
+        for i in range(1, m):
+            k = fail[i]
+            while k and opener[i] != opener[k]:
+                k = fail[k]
+            fail[i + 1] = k + 1 if opener[i] == opener[k] else 0
+        free = [new() for _ in range(m)]
+        for i in range(m):
+            masks_to: Dict[int, int] = {}
+            for byte in range(256):
+                k = i
+                while k and opener[k] != byte:
+                    k = fail[k]
+                k = k + 1 if opener[k] == byte else 0
+                masks_to[k] = masks_to.get(k, 0) | (1 << byte)
+            for k, mk in masks_to.items():
+                edges[free[i]].append((mk, n_start if k == m else free[k]))
+        n_start = free[0]
     # byte classes of the NFA's masks: subset construction runs per class, not per byte
     masks = sorted({m for es in edges for m, _ in es})
     sig: Dict[tuple, int] = {}
@@ -833,11 +862,21 @@ def canonical_spec(spec) -> str:
     if not isinstance(spec, dict) or not isinstance(spec.get("type"), str):
         raise ValueError('grammar must be {"type": "json_object" | "json_schema" | "regex", ...}')
     t = spec["type"]
-    want = {"json_object": {"type"}, "json_schema": {"type", "schema"}, "regex": {"type", "pattern"}}.get(t)
+    want = {"json_object": {"type"}, "json_schema": {"type", "schema"}, "regex": {"type", "pattern"},
+            "tail": {"type", "open", "body", "close"}}.get(t)
     if want is None:
         raise ValueError(f"unknown grammar type {t!r}")
     if set(spec) != want:
         raise ValueError(f"a {t} grammar takes exactly the fields {sorted(want)}")
+    if t == "tail":
+        for k, lo in (("open", 1), ("close", 0)):
+            v = spec[k]
+            if not isinstance(v, str) or not lo <= len(v.encode("utf-8")) <= TAIL_MAX_BYTES:
+                raise ValueError(f"a tail grammar's {k!r} must be a string of {lo}..{TAIL_MAX_BYTES} bytes")
+        body = spec["body"]
+        if not isinstance(body, dict) or body.get("type") not in ("json_schema", "regex"):
+            raise ValueError("a tail grammar's 'body' must be a json_schema or regex grammar")
+        canonical_spec(body)
     try:
         return json.dumps(spec, ensure_ascii=False, allow_nan=False)
     except (TypeError, ValueError) as e:
@@ -852,6 +891,11 @@ def _compile(key: str) -> CompiledGrammar:
         return _build_json(key)
     if t == "regex":
         return _ast_to_grammar("regex", key, parse_regex(spec["pattern"]))
+    if t == "tail":
+        body = spec["body"]
+        ast = parse_regex(body["pattern"]) if body["type"] == "regex" else schema_to_ast(body["schema"])
+        return _ast_to_grammar("tail", key, ("cat", [ast, lit(spec["close"].encode("utf-8"))]),
+                               opener=spec["open"].encode("utf-8"))
     return _ast_to_grammar("json_schema", key, schema_to_ast(spec["schema"]))
 
 
@@ -1080,6 +1124,160 @@ class BoundGrammar:
         for t in tokens:
             st = self.advance(st, int(t))
         return st
+
+    def budget(self) -> "GrammarBudget":
+        """The pair's :class:`GrammarBudget` (cached). ValueError when a state can only be left by
+        multi-byte tokens: the bound on the tokens a document still needs rests on single-byte ones."""
+        b = self.__dict__.get("_budget")
+        if b is None:
+            b = self._budget = GrammarBudget(self)
+        return b
+
+    def all_live(self) -> bytes:
+        """Per state: every token with usable bytes stays live from it (cached; :class:`GrammarBudget`)."""
+        f = self.__dict__.get("_all_live")
+        if f is None:
+            f = self._all_live = GrammarBudget._all_live(self.g, self.table)
+        return f
+
+    def token_allowed_budget(self, state: State, tok: int, r: int) -> bool:
+        """:meth:`token_allowed` under the budget rule (:class:`GrammarBudget`), ``r`` tokens left."""
+        if tok in self._stops:      # r <= 0 behaves like DEAD: stop ids only
+            return r <= 0 or state[0] < 0 or self.g.is_accepting(state)
+        return r > 0 and self.token_allowed(state, tok) and self.budget().need(self.advance(state, tok)) <= r - 2
+
+
+class GrammarBudget:
+    """What the budgeted mask (csrc/grammar_budget.hip) reads beside the automaton, for one bound pair.
+
+    ``need(state)`` is an upper bound on the tokens that still lead from ``state`` to an accepting
+    state, along byte classes that have a single-byte token (so every step of that path is one token
+    whatever the stack holds):
+
+    * ``c_pop[q]``: the fewest such tokens up to and including the next pop, over edges without an
+      action (a push is never needed to close what is open);
+    * ``c_acc[q]``, for depth 0: the fewest tokens to an accepting state, where a push edge to ``t``
+      costs ``1 + c_pop[t] + c_acc0[pop_empty]`` (``c_acc0``: the same without push edges);
+    * ``need = c_acc[q]`` at depth 0, else ``c_pop[q]`` + one ``c_pop[pop_target[bit]]`` per stack level
+      below the top + ``c_acc[pop_empty]``: two popcounts.
+
+    The first token of the path that defines ``need`` lowers it by at least one. So with ``r`` tokens
+    left (the one sampled now included) and the rule "a non-stop token is allowed iff its walk stays
+    live and ``need(state after it) <= r - 2``", ``need(state) <= r - 1`` holds at every step once it holds
+    at the start; some token is always allowed; and at ``r = 1`` the state accepts, so the stop id ends
+    the reply inside the budget. Entries are 16-bit, ``NEED_INF16`` for none.
+
+    ``all_live[q]``: every token with usable bytes stays live from ``q`` (the free states of a ``tail``
+    grammar; a token that holds the whole opener and then a bad byte clears it). ``need_cap``: the
+    largest ``need`` of a regular grammar; in a flagged state with ``r - 2 >= need_cap`` the rule allows
+    every token with bytes, and the kernel walks none."""
+
+    def __init__(self, bound: "BoundGrammar"):
+        import heapq
+        g, table = bound.g, bound.table
+        n, ncls = g.n_states, g.n_classes
+        single = sorted({g.cls[p[0]] for p in table.pieces if len(p) == 1})
+        inf = NEED_INF
+        rev: List[List[int]] = [[] for _ in range(n)]          # edges without an action, reversed
+        pushes: List[Tuple[int, int]] = []
+        c_pop = [inf] * n
+        for q in range(n):
+            for c in single:
+                e = g.trans[q * ncls + c]
+                if e == DEAD_ENTRY:
+                    continue
+                if (e & 3) == ACT_POP:
+                    c_pop[q] = 1
+                elif e & 3:
+                    pushes.append((q, e >> 2))
+                else:
+                    rev[e >> 2].append(q)
+
+        def spread(cost: List[int]) -> List[int]:
+            """Shortest costs to the seeded states over the unit edges of ``rev``."""
+            heap = [(c, q) for q, c in enumerate(cost) if c < inf]
+            heapq.heapify(heap)
+            while heap:
+                c, q = heapq.heappop(heap)
+                if c > cost[q]:
+                    continue
+                for p in rev[q]:
+                    if c + 1 < cost[p]:
+                        cost[p] = c + 1
+                        heapq.heappush(heap, (c + 1, p))
+            return cost
+
+        c_pop = spread(c_pop)
+        seed = [0 if a else inf for a in g.accept]
+        c_acc = spread(list(seed))
+        pe = g.pop_target[2]
+        if g.uses_stack and pe >= 0 and c_acc[pe] < inf:
+            for q, t in pushes:        # a push at depth 0: its container closes, then pop_empty's way to accept
+                seed[q] = min(seed[q], 1 + c_pop[t] + c_acc[pe])
+            c_acc = spread(seed)
+        bad = [q for q in range(n) if min(c_acc[q], c_pop[q] if g.uses_stack else inf) >= NEED_INF16]
+        if g.uses_stack:
+            bad += [p for p, c in zip(g.pop_target, (c_pop, c_pop, c_acc)) if p >= 0 and c[p] >= NEED_INF16]
+        if bad:
+            raise ValueError(f"the {g.kind} grammar cannot finish inside a budget with tokenizer {table.name!r}: "
+                             f"state {bad[0]} can only be left by multi-byte tokens")
+        self.g = g
+        self.c_acc = [min(c, NEED_INF16) for c in c_acc]
+        self.c_pop = [min(c, NEED_INF16) for c in c_pop]
+        self.need_cap = NEED_INF if g.uses_stack else max(self.c_acc)
+        self.all_live = bound.all_live()
+        self.need_start = self.need(g.start_state)
+
+    def need(self, state: State) -> int:
+        """csrc/grammar_core.h ``need``. 0 for ``FIN`` / ``DEAD``: only stop ids follow."""
+        q, depth, stack = state
+        if q < 0:
+            return 0
+        pobj, parr, pempty = self.g.pop_target
+        if depth == 0:
+            parts = [(self.c_acc[q], 1)]
+        else:
+            ones = bin(stack & ((1 << (depth - 1)) - 1)).count("1")
+            parts = [(self.c_pop[q], 1), (self.c_pop[pobj] if pobj >= 0 else NEED_INF16, depth - 1 - ones),
+                     (self.c_pop[parr] if parr >= 0 else NEED_INF16, ones),
+                     (self.c_acc[pempty] if pempty >= 0 else NEED_INF16, 1)]
+        if any(c == NEED_INF16 and k for c, k in parts):
+            return NEED_INF
+        return sum(c * k for c, k in parts)
+
+    def min_tokens(self) -> int:
+        """The smallest ``max_new_tokens`` the rule can start from: ``need(start)`` and the stop id."""
+        return self.need_start + 1
+
+    @staticmethod
+    def _all_live(g: CompiledGrammar, table: TokenTable) -> bytes:
+        ids = table.by_len
+        n, ncls = g.n_states, g.n_classes
+        flags = bytearray(n)
+        if g.uses_stack or not ids:
+            return bytes(flags)
+        firsts = sorted({g.cls[table.pieces[i][0]] for i in ids})
+        cand = [q for q in range(n) if all(g.trans[q * ncls + c] != DEAD_ENTRY for c in firsts)]
+        if not cand:
+            return bytes(flags)
+        import torch       # every token walked at once, one byte position per iteration
+        lens = torch.tensor([len(table.pieces[i]) for i in ids], dtype=torch.int64)       # ascending
+        off = torch.cumsum(lens, 0) - lens
+        flat = torch.frombuffer(bytearray(b"".join(table.pieces[i] for i in ids)), dtype=torch.uint8).long()
+        cls = torch.tensor(list(g.cls), dtype=torch.int64)[flat]
+        trans = torch.tensor(g.trans, dtype=torch.int64)
+        for q0 in cand:
+            q = torch.full((len(ids),), q0, dtype=torch.int64)
+            ok = True
+            for p in range(int(lens[-1])):
+                lo = int(torch.searchsorted(lens, p, right=True))      # tokens longer than p
+                e = trans[q[lo:] * ncls + cls[off[lo:] + p]]
+                if bool((e == DEAD_ENTRY).any()):
+                    ok = False
+                    break
+                q[lo:] = e >> 2
+            flags[q0] = 1 if ok else 0
+        return bytes(flags)
 
 
 def bind(spec, tokenizer, vocab: int) -> BoundGrammar:

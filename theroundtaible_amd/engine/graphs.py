@@ -55,7 +55,7 @@ def no_gc_during_capture():
 
 class DecodeGraph:
     def __init__(self, engine, bucket: int, splits: int, grouped: bool = False, dist_greedy: bool = False,
-                 capture: bool = True, processors: bool = False, logprobs: bool = False, grammar: bool = False):
+                 capture: bool = True, processors: bool = False, logprobs: bool = False, grammar=False):
         self.engine = engine
         self.B = bucket
         self.splits = splits
@@ -104,7 +104,10 @@ class DecodeGraph:
         # grammar: such a graph owns the rows' automata and the two-slot state; the captured mask kernel
         # advances each row's state over the token K6 recorded in the previous replay
         assert not (grammar and dist_greedy), "the (value, id) gather never sees masked rows"
-        self.gm = ops.GrammarMask(B, dev, engine.token_table()) if grammar else None
+        # (grammar == "grb": the budgeted launch and its operands, for a batch with a grammar_finish or tail row)
+        self.gm_budget = grammar == "grb"
+        self.gm = ((ops.GrammarBudgetMask if self.gm_budget else ops.GrammarMask)(B, dev, engine.token_table())
+                   if grammar else None)
         self.graph = None
         self._host_out: List[torch.Tensor] = []
         if capture:     # (Engine._agreed_graph agrees on the buffers first, then captures)
@@ -148,7 +151,7 @@ class DecodeGraph:
             ops.apply_logit_processors(logits, self.proc, self.out, self.step)
         if self.gm is not None:     # after the processors, before K6
             logits = logits.contiguous()
-            ops.apply_grammar_mask(logits, self.gm, self.out, self.step)
+            (ops.apply_grammar_mask_budget if self.gm_budget else ops.apply_grammar_mask)(logits, self.gm, self.out, self.step)
         if fused and not self.dist_greedy:
             # ONE launch: K6 sampling + record / advance + the next step's slots, offsets, embeddings
             ops.sample_advance(logits.contiguous(), self.temp, self.top_p, self.top_k, self.seeds, offsets,
@@ -260,8 +263,8 @@ class DecodeGraph:
                            + [None] * pad)
         if self.gm is not None:     # tables and, in slot 0, the state after the reply tokens the host holds
             starts = reply_starts if reply_starts is not None else [s.length for s in seqs]
-            self.gm.fill(engine.grammar_rows(turns, [(s.tokens + [f])[r:] for s, f, r in zip(seqs, first_host, starts)])
-                         + [None] * pad)
+            self.gm.fill(engine.grammar_rows(turns, [(s.tokens + [f])[r:] for s, f, r in zip(seqs, first_host, starts)],
+                                             self.gm_budget) + [None] * pad)
         if self.lp is not None:
             self.lp.fill([t.params for t in turns] + [None] * pad)
         with torch.no_grad():

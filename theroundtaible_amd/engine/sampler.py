@@ -35,15 +35,37 @@ class SamplingParams:
     # {"type": "json_object"} | {"type": "json_schema", "schema": {...}} | {"type": "regex", "pattern": "..."}.
     # Tokens the grammar cannot accept next get -inf after the processors above and before sampling;
     # the reply ends with a stop id once the grammar accepts (or is cut short by max_new_tokens).
+    # Also {"type": "tail", "open": "...", "body": <json_schema or regex spec>, "close": "..."}: free text up to
+    # the first ``open``, then the body, then ``close`` (a grammar that switches on mid-reply).
     grammar: Optional[dict] = None
+    # with a grammar: the reply's ids end with a stop id after at most max_new_tokens tokens and the text
+    # before it is accepted by the grammar (csrc/grammar_budget.hip masks by the tokens left as well).
+    # max_new_tokens below the grammar's minimum is a ValueError before prefill.
+    grammar_finish: bool = False
+    # set by the engine when max_new_tokens is a decode chunk's, not the reply's: the reply's whole budget
+    grammar_budget: Optional[int] = None
 
     def wants_grammar(self) -> bool:
         return self.grammar is not None
+
+    def wants_grammar_budget(self) -> bool:
+        """The row needs the budgeted mask launch: ``grammar_finish``, or a ``tail`` grammar (its free phase
+        is that launch's shortcut)."""
+        return self.grammar is not None and (self.grammar_finish or (isinstance(self.grammar, dict)
+                                                                      and self.grammar.get("type") == "tail"))
+
+    def reply_budget(self) -> Optional[int]:
+        """Tokens the whole reply may hold under ``grammar_finish``; None when nothing bounds the grammar."""
+        if self.grammar is None or not self.grammar_finish:
+            return None
+        return int(self.grammar_budget if self.grammar_budget is not None else max(1, self.max_new_tokens))
 
     def check_grammar(self) -> None:
         """ValueError for a spec the compiler refuses and for ``ignore_eos`` with a grammar: a
         constrained reply ends with a stop id (serve.py answers 400)."""
         if self.grammar is None:
+            if self.grammar_finish:
+                raise ValueError("grammar_finish needs a grammar")
             return
         from .grammar import compile_grammar
         compile_grammar(self.grammar)

@@ -31,6 +31,9 @@ class TurnRequest:
     # prompt as far as those results determine it (or None). A distributed pool calls it while
     # the C1 exchange of the remote results is in flight and prefetches that prefix.
     speculate: Optional[Callable[[Dict[str, "TurnResult"]], Optional[PromptLike]]] = None
+    # the orchestrator hands this turn's reply to parse_consensus (a discussion turn; not apply / code-red):
+    # an engine knight with ``engine.consensus_grammar`` constrains such a reply's closing block
+    consensus: bool = False
 
 
 @dataclass

@@ -12,6 +12,7 @@ import threading
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 from ..config import resolve_weight_quant
+from ..consensus import consensus_grammar
 from ..engine.engine import Engine, EngineConfig, Turn
 from ..engine.sampler import SamplingParams
 from .base import KnightBackend, TurnRequest, TurnResult
@@ -25,13 +26,15 @@ ADAPTER_DISPLAY_NAMES = {
 
 class EngineBackend(KnightBackend):
     def __init__(self, name: str, adapter_id: str, engine: Engine, params: SamplingParams,
-                 lock: Optional[threading.Lock] = None, script: Optional[ConsensusScript] = None):
+                 lock: Optional[threading.Lock] = None, script: Optional[ConsensusScript] = None,
+                 consensus_grammar: bool = False):
         self.name = name
         self.adapter_id = adapter_id
         self.engine = engine
         self.params = params
         self.lock = lock or threading.Lock()
         self.script = script
+        self.consensus_grammar = consensus_grammar      # engine.consensus_grammar (config.engine_settings)
 
     def group_key(self):
         return id(self.engine)
@@ -51,6 +54,11 @@ class EngineBackend(KnightBackend):
             p = SamplingParams(**{**p.__dict__, "max_new_tokens": min(p.max_new_tokens, self.script.free_tokens),
                                   "stop_on_consensus": False,
                                   "forced_tail": self.script.tail(knight, req.round, req.seq_key)})
+        if self.consensus_grammar and req.consensus:
+            # free text, then the fenced consensus block, then a stop id, inside max_new_tokens: the grammar
+            # ends the reply itself, so nothing is cut at the block
+            p = SamplingParams(**{**p.__dict__, "grammar": consensus_grammar(), "grammar_finish": True,
+                                  "stop_on_consensus": False})
         return Turn(req.seq_key, req.prompt, p, timeout_s)
 
     def execute_group(self, pairs: Sequence[Tuple["EngineBackend", TurnRequest]],

@@ -105,7 +105,8 @@ class BackendFactory:
                                 stop_on_consensus=bool(st.get("stop_on_consensus", True)),
                                 **processor_settings(st))
         return EngineBackend(name, adapter_id, engine, params, lock,
-                             script=ConsensusScript.from_config(st.get("scripted_consensus")))
+                             script=ConsensusScript.from_config(st.get("scripted_consensus")),
+                             consensus_grammar=bool(st.get("consensus_grammar", False)))
 
     __call__ = create
 

@@ -112,7 +112,8 @@ def build_spmd_backends(config: RoundtableConfig, cluster: Cluster, ui: UI = NUL
                                 stop_on_consensus=bool(st.get("stop_on_consensus", True)),
                                 **processor_settings(st))
         local[aid] = EngineBackend(display_name(aid, config), aid, engine, params, lock,
-                                   script=ConsensusScript.from_config(st.get("scripted_consensus")))
+                                   script=ConsensusScript.from_config(st.get("scripted_consensus")),
+                                   consensus_grammar=bool(st.get("consensus_grammar", False)))
         ui.ok(f"  ✓ {k.name}: {st['model']} on rank(s) {ranks}" + (f" (tp={len(ranks)})" if len(ranks) > 1 else ""))
     # no rank enters a turn-time (short-timeout) collective before every rank has loaded its
     # engines: ranks load one engine after another, a real checkpoint can take minutes longer on

@@ -865,3 +865,76 @@ def apply_grammar_mask(logits: torch.Tensor, gm: GrammarMask, out: Optional[torc
                               gm.tok_bytes, out if step is not None else None, step)
         return logits
     return ref.apply_grammar_mask(logits, gm, out if step is not None else None, step)
+
+
+class GrammarBudgetMask(GrammarMask):
+    """:class:`GrammarMask` plus what the budgeted launch reads per row: ``budget`` [B] int32 (tokens the
+    row may still emit when the launch's step is 0), ``need`` [2, B, 4096] int16 (16-bit ``c_acc`` /
+    ``c_pop`` entries of ``engine.grammar.GrammarBudget``), ``all_live`` [B, 4096] uint8 and ``need_cap`` in
+    ``meta[:, 7]``. A row given without a budget gets ``BUDGET_FREE`` and zero need arrays: nothing binds
+    and its mask is :func:`apply_grammar_mask`'s."""
+
+    def __init__(self, batch: int, device, table):
+        super().__init__(batch, device, table)
+        self.budget = torch.full((batch,), ref.GRAMMAR_BUDGET_FREE, dtype=torch.int32, device=device)
+        self.need = torch.zeros(2, batch, GRAMMAR_MAX_STATES, dtype=torch.int16, device=device)
+        self.all_live = torch.zeros(batch, GRAMMAR_MAX_STATES, dtype=torch.uint8, device=device)
+
+    def fill(self, rows) -> "GrammarBudgetMask":
+        """``rows``: per batch row ``(bound, state, budget)`` or None; ``budget`` None for a row nothing
+        bounds, else ``max_new_tokens`` less the reply tokens the host holds (``state`` is the state
+        after them). ValueError from ``bound.budget()`` for a pair that cannot finish inside a budget."""
+        super().fill([None if r is None else (r[0], r[1]) for r in rows])
+        self._ref_rows = {}      # (ops/reference.py keeps each row's host copy between fills)
+        B = self.meta.shape[0]
+        dev = self.meta.device
+        budget = torch.full((B,), ref.GRAMMAR_BUDGET_FREE, dtype=torch.int32)
+        cap = torch.zeros(B, dtype=torch.int32)
+        for b, row in enumerate(rows):
+            if row is None:
+                continue
+            bound, _, left = row
+            n = bound.g.n_states
+            need = torch.zeros(2, n, dtype=torch.int16)
+            if left is not None:
+                bd = bound.budget()
+                budget[b] = max(-1, min(int(left), ref.GRAMMAR_BUDGET_FREE))
+                cap[b] = min(bd.need_cap, ref.GRAMMAR_NEED_INF)
+                need = _need_host_tensor(bd)
+            self.need[:, b, :n].copy_(need.to(dev, non_blocking=True))
+            self.all_live[b, :n].copy_(torch.tensor(list(bound.all_live()), dtype=torch.uint8).to(dev, non_blocking=True))
+        self.budget.copy_(budget.to(dev, non_blocking=True))
+        self.meta[:, 7].copy_(cap.to(dev, non_blocking=True))
+        return self
+
+    def set_budgets(self, budgets) -> "GrammarBudgetMask":
+        """``budget`` only: per row the tokens left, or None for a row nothing bounds (the eager path's
+        per-step update, beside :meth:`set_states`)."""
+        v = torch.tensor([ref.GRAMMAR_BUDGET_FREE if x is None else max(-1, min(int(x), ref.GRAMMAR_BUDGET_FREE))
+                          for x in budgets], dtype=torch.int32)
+        self.budget[:v.shape[0]].copy_(v.to(self.budget.device, non_blocking=True))
+        return self
+
+
+def _need_host_tensor(bd):
+    """int16 [2, n_states] (c_acc, c_pop as 16-bit entries) of a GrammarBudget, cached on it."""
+    t = getattr(bd, "_host_need", None)
+    if t is None:
+        t = bd._host_need = torch.tensor([[e - 65536 if e >= 32768 else e for e in arr] for arr in (bd.c_acc, bd.c_pop)],
+                                         dtype=torch.int16)
+    return t
+
+
+def apply_grammar_mask_budget(logits: torch.Tensor, gm: GrammarBudgetMask, out: Optional[torch.Tensor] = None,
+                              step: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`apply_grammar_mask` under each row's token budget (csrc/grammar_budget.hip; semantics:
+    ops/reference.py): with ``r = gm.budget[b] - step`` tokens left, a non-stop token is allowed iff its walk
+    stays live and ``need(state after it) <= r - 2``; ``r <= 0`` allows stop ids only. In a state flagged
+    all-live with ``need_cap <= r - 2`` the kernel walks no token. Capturable with ``out`` and ``step``."""
+    if logits.shape[1] > gm.table.vocab:
+        raise ValueError(f"the token table covers {gm.table.vocab} ids, the logits have {logits.shape[1]}")
+    if _use_native(logits):
+        native().grammar_mask_budget(logits, gm.meta, gm.cls, gm.tab, gm.accept, gm.stops, gm.state, gm.tok_off,
+                                     gm.tok_bytes, gm.budget, gm.need, gm.all_live, out if step is not None else None, step)
+        return logits
+    return ref.apply_grammar_mask_budget(logits, gm, out if step is not None else None, step)

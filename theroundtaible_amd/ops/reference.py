@@ -626,21 +626,22 @@ def grammar_advance(row: GrammarRow, st, tok: int, V: int):
     return grammar_walk(row, st, data) if data else (GRAMMAR_Q_DEAD, 0, 0)
 
 
-def grammar_allowed(row: GrammarRow, st, V: int) -> torch.Tensor:
-    """bool [V]: the tokens the mask kernel leaves untouched at state ``st`` (every token walked at once,
-    one byte position per iteration)."""
+def grammar_walk_all(row: GrammarRow, st, V: int):
+    """Every token of [0, V) walked at once from state ``st``, one byte position per iteration:
+    ``(alive bool [V], q, depth, stack int64 [V])``, the last three meaningful where ``alive``. A state
+    outside the table walks nothing."""
     q0, d0, s0 = st
     if q0 >= row.ns or not 0 <= d0 <= GRAMMAR_MAX_DEPTH:
         q0 = GRAMMAR_Q_DEAD
-    allowed = torch.zeros(V, dtype=torch.bool)
+    q = torch.full((V,), q0, dtype=torch.int64)
+    depth = torch.full((V,), d0, dtype=torch.int64)
+    stack = torch.full((V,), s0 & 0xFFFFFFFF, dtype=torch.int64)
+    alive = torch.zeros(V, dtype=torch.bool)
     if q0 >= 0:
         lo, hi = row.tok_off[:V], row.tok_off[1:V + 1]
         lens = hi - lo
         alive = (lens > 0) & (lens <= GRAMMAR_TOKEN_BYTE_CAP) & (lo >= 0) & (hi <= row.tok_bytes.numel())
         lens = torch.where(alive, lens, torch.zeros_like(lens))
-        q = torch.full((V,), q0, dtype=torch.int64)
-        depth = torch.full((V,), d0, dtype=torch.int64)
-        stack = torch.full((V,), s0 & 0xFFFFFFFF, dtype=torch.int64)
         pops = torch.tensor(row.pops, dtype=torch.int64)
         one = torch.ones(1, dtype=torch.int64)
         for p in range(int(lens.max()) if V else 0):
@@ -666,7 +667,13 @@ def grammar_allowed(row: GrammarRow, st, V: int) -> torch.Tensor:
             q[ik] = qn[keep]
             depth[ik] = torch.where(pop, d_pop, torch.where(push, d + 1, d))[keep]
             stack[ik] = torch.where(pop, s_pop, torch.where(push, s_push, s))[keep]
-        allowed = alive
+    return alive, q, depth, stack
+
+
+def grammar_allowed(row: GrammarRow, st, V: int) -> torch.Tensor:
+    """bool [V]: the tokens the mask kernel leaves untouched at state ``st``."""
+    allowed = grammar_walk_all(row, st, V)[0]
+    q0 = st[0] if st[0] < row.ns and 0 <= st[1] <= GRAMMAR_MAX_DEPTH else GRAMMAR_Q_DEAD
     stop_ok = q0 < 0 or bool(row.accept[q0])
     for t in row.stops:
         if 0 <= t < V:
@@ -702,5 +709,81 @@ def apply_grammar_mask(logits: torch.Tensor, gm, out=None, step=None) -> torch.T
             stack = st[2] - (1 << 32) if st[2] >= (1 << 31) else st[2]
             gm.state[slot, b] = torch.tensor([st[0], st[1], stack, 0], dtype=torch.int32).to(gm.state.device)
         allowed = grammar_allowed(row, st, V)
+        logits[b, :V][~allowed.to(logits.device)] = float("-inf")
+    return logits
+
+
+# ---- budgeted grammar mask (csrc/grammar_budget.hip; the bound and the rule: csrc/grammar_core.h) ------
+
+GRAMMAR_NEED_INF16 = 0xFFFF           # engine/grammar.py holds the same three
+GRAMMAR_NEED_INF = 1 << 30
+GRAMMAR_BUDGET_FREE = 1 << 29
+
+
+def grammar_need(row: GrammarRow, c_acc: torch.Tensor, c_pop: torch.Tensor, q, depth, stack) -> torch.Tensor:
+    """grammar_core.h ``need`` over vectors of live states (int64): ``c_acc[q]`` at depth 0, else ``c_pop[q]``
+    + one ``c_pop[pop target]`` per stack level below the top + ``c_acc[pop_empty]``; ``NEED_INF`` where a
+    16-bit entry it reads says none."""
+    inf16 = GRAMMAR_NEED_INF16
+    pobj, parr, pempty = row.pops
+    ent = lambda arr, p: int(arr[p]) if 0 <= p < row.ns else inf16        # noqa: E731
+    qc = q.clamp(0, max(row.ns - 1, 0))
+    below = torch.bitwise_left_shift(torch.ones_like(depth), (depth - 1).clamp(min=0)) - 1
+    m = stack & below
+    ones = torch.zeros_like(depth)
+    for i in range(GRAMMAR_MAX_DEPTH):
+        ones += torch.bitwise_right_shift(m, i) & 1
+    zeros = (depth - 1 - ones).clamp(min=0)
+    a, p = c_acc[qc], c_pop[qc]
+    eo, ea, ee = ent(c_pop, pobj), ent(c_pop, parr), ent(c_acc, pempty)
+    deep = p + zeros * eo + ones * ea + ee
+    bad = (p == inf16) | (ee == inf16) | ((zeros > 0) & (eo == inf16)) | ((ones > 0) & (ea == inf16))
+    deep = torch.where(bad, torch.full_like(deep, GRAMMAR_NEED_INF), deep)
+    flat = torch.where(a == inf16, torch.full_like(a, GRAMMAR_NEED_INF), a)
+    return torch.where(depth == 0, flat, deep)
+
+
+def grammar_allowed_budget(row: GrammarRow, st, V: int, r: int, c_acc: torch.Tensor, c_pop: torch.Tensor):
+    """bool [V] under the budget rule with ``r`` tokens left, and the need after each allowed token
+    (int64 [V], meaningful where a non-stop token is allowed). The all-live flags and ``need_cap`` only
+    let the kernel skip work: they are not read here."""
+    if r <= 0 and st[0] >= 0:
+        st = (GRAMMAR_Q_DEAD, 0, 0)
+    walks = row.__dict__.setdefault("_walks", {})      # a reply revisits few states (free text, a string's inside)
+    if (st, V) not in walks and len(walks) >= 64:
+        walks.clear()
+    alive, q, depth, stack = walks.get((st, V)) or walks.setdefault((st, V), grammar_walk_all(row, st, V))
+    alive = alive.clone()
+    need = torch.zeros(V, dtype=torch.int64)
+    if bool(alive.any()):
+        idx = torch.nonzero(alive).squeeze(1)
+        need[idx] = grammar_need(row, c_acc, c_pop, q[idx], depth[idx], stack[idx])
+        alive &= need <= r - 2
+    q0 = st[0] if st[0] < row.ns and 0 <= st[1] <= GRAMMAR_MAX_DEPTH else GRAMMAR_Q_DEAD
+    stop_ok = q0 < 0 or bool(row.accept[q0])
+    for t in row.stops:
+        if 0 <= t < V:
+            alive[t] = stop_ok
+    return alive, need
+
+
+def apply_grammar_mask_budget(logits: torch.Tensor, gm, out=None, step=None) -> torch.Tensor:
+    """Semantics of csrc/grammar_budget.hip (in place): :func:`apply_grammar_mask` where, with
+    ``r = gm.budget[b] - step`` tokens left, a non-stop token must also leave ``need(state after it) <= r - 2``
+    and ``r <= 0`` allows stop ids only. State hand-over as in :func:`apply_grammar_mask`."""
+    B, V = logits.shape
+    s = int(step.reshape(-1)[0]) if step is not None and out is not None else 0
+    for b in range(B):
+        if int(gm.meta[b, 0]) == 0:
+            continue
+        rows = gm.__dict__.setdefault("_ref_rows", {})      # a row's host copy, until the next fill()
+        row = rows.get(b) or rows.setdefault(b, GrammarRow(gm, b))
+        st, slot = grammar_step_state(gm, row, b, V, out, step)
+        if slot is not None:
+            stack = st[2] - (1 << 32) if st[2] >= (1 << 31) else st[2]
+            gm.state[slot, b] = torch.tensor([st[0], st[1], stack, 0], dtype=torch.int32).to(gm.state.device)
+        r = max(-1, min(int(gm.budget[b]) - max(s, 0), GRAMMAR_BUDGET_FREE))
+        allowed, _ = grammar_allowed_budget(row, st, V, r, gm.need[0, b].cpu().long() & 0xFFFF,
+                                            gm.need[1, b].cpu().long() & 0xFFFF)
         logits[b, :V][~allowed.to(logits.device)] = float("-inf")
     return logits

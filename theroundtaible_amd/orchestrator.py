@@ -320,7 +320,7 @@ class Orchestrator:
                 continue
             prompt = self._prompt(knight, self.ctx, visible, rnd, self.cont is not None, files, cmds)
             plan.append((knight, backend, TurnRequest(self.table_id + knight.name, prompt, rnd, self.opt.max_new_tokens,
-                                                      speculate=predict)))
+                                                      speculate=predict, consensus=True)))
         self.store.update_status(self.session_path, phase="discussing", current_knight=None, round=rnd)
         return plan
 
@@ -380,7 +380,8 @@ class Orchestrator:
                               self.tool_state["files"], self.tool_state["commands"])
         msgs = THINKING.get(knight.name, ["is thinking...", "prepares their response..."])
         self.ui.print(f"  {knight.name} {msgs[self.rng.randrange(len(msgs))]}", "dim")
-        return knight, backend, TurnRequest(self.table_id + knight.name, prompt, rnd, self.opt.max_new_tokens)
+        return knight, backend, TurnRequest(self.table_id + knight.name, prompt, rnd, self.opt.max_new_tokens,
+                                            consensus=True)
 
     def record_turn(self, rnd: int, knight: KnightConfig, backend: KnightBackend,
                     res: Union[TurnResult, BaseException]) -> None:

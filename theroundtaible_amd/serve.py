@@ -762,14 +762,31 @@ class RoundtableServer:
                                 repeat_last_n=num("repeat_last_n", 64, int),
                                 presence_penalty=num("presence_penalty", 0.0, float),
                                 frequency_penalty=num("frequency_penalty", 0.0, float), logit_bias=bias or None,
-                                logprobs=self.logprob_request(body), grammar=self.grammar_request(body))
+                                logprobs=self.logprob_request(body), grammar=self.grammar_request(body),
+                                grammar_finish=self.finish_request(body))
+        if params.grammar_finish and params.grammar is None:
+            raise ValueError("'guided_finish' needs a grammar: 'response_format' (json_object / json_schema) or 'guided_regex'")
         params.check_processors(int(self.engine.cfg.vocab))      # ValueError -> HTTP 400
         params.check_logprobs()
         params.check_grammar()
         if params.wants_grammar():      # a tokenizer the grammar cannot be bound to is a 400 too
+            from .engine.engine import check_budget
             from .engine.grammar import bind
-            bind(params.grammar, self.engine.tokenizer, int(self.engine.cfg.vocab))
+            bound = bind(params.grammar, self.engine.tokenizer, int(self.engine.cfg.vocab))
+            if params.grammar_finish:   # and a max_tokens below the grammar's minimum (the message states it)
+                check_budget(bound, params.reply_budget())
         return params
+
+    @staticmethod
+    def finish_request(body: Dict[str, Any]) -> bool:
+        """The extension ``guided_finish`` (OpenAI completion endpoints): with a grammar field, the reply
+        ends with a stop id inside ``max_tokens`` and always parses. ValueError (HTTP 400) unless a bool."""
+        v = body.get("guided_finish")
+        if v is None:
+            return False
+        if not isinstance(v, bool):
+            raise ValueError("'guided_finish' must be true or false")
+        return v
 
     @staticmethod
     def grammar_request(body: Dict[str, Any]) -> Optional[Dict[str, Any]]:
@@ -896,9 +913,11 @@ class RoundtableServer:
             raise RuntimeError(str(r.error))
         return r.result, r
 
-    @staticmethod
-    def finish(out, r: _Request) -> str:
+    def finish(self, out, r: _Request) -> str:
         if out.metrics.get("stop_string"):
+            return "stop"
+        # guided_finish spends its budget down to the last token, and that token is the stop id
+        if r.params.grammar_finish and out.ids and out.ids[-1] in self.engine.tokenizer.stop_ids:
             return "stop"
         return "length" if len(out.ids) >= r.params.max_new_tokens else "stop"
 
