@@ -118,6 +118,16 @@ int launch_skinny_gemm_rope_fp8(void* q_out, const void* x, const void* Wq, cons
                                 float eps, const int64_t* positions, const float* cos_sin, void* k_cache,
                                 void* v_cache, const int64_t* slots, int Hq, int Hkv, int D, int BS,
                                 const float* bias, hipStream_t stream);
+int launch_shuffle_weight_fp4(void* Wq, uint8_t* scale, const void* W, const void* gamma, int N, int K,
+                              int rope_rows, int D, int swiglu, hipStream_t stream);
+int launch_unshuffle_weight_fp4(void* W, const void* Wq, const uint8_t* scale, int N, int K, int rope_rows, int D,
+                                int swiglu, hipStream_t stream);
+int launch_skinny_gemm_fp4(void* out, const void* x, const void* Wq, const uint8_t* scale, void* res, int M, int N,
+                           int K, int ldo, float eps, int pro, int epi, const void* rope, hipStream_t stream);
+int launch_skinny_gemm_rope_fp4(void* q_out, const void* x, const void* Wq, const uint8_t* scale, int M, int K,
+                                int pro, float eps, const int64_t* positions, const float* cos_sin, void* k_cache,
+                                void* v_cache, const int64_t* slots, int Hq, int Hkv, int D, int BS,
+                                const float* bias, hipStream_t stream);
 
 
 namespace {
@@ -993,6 +1003,86 @@ void skinny_gemm_rope_fp8(torch::Tensor q_out, torch::Tensor x, torch::Tensor Wq
                                              (int)k_cache.size(2), bp, cur_stream());
   TORCH_CHECK(rc == 0, "skinny_gemm_rope_fp8: unsupported configuration (rc=", rc, ")");
 }
+
+// ---- MXFP4 weight-only decode GEMMs (quantiser: csrc/gemm_skinny_fp4.hip, launches: gemm_skinny.hip) ----
+// codes uint8 [N, K/2] (two e2m1 codes per byte), scale bytes uint8 [N, K/32] (one per block of 32 k)
+void check_fp4_weight(const torch::Tensor& Wq, const torch::Tensor& scale, int64_t rows, int64_t K, const char* who) {
+  check_type(Wq, torch::kUInt8, "Wq");
+  check_type(scale, torch::kUInt8, "wscale");
+  TORCH_CHECK(K % 128 == 0 && rows % 16 == 0 && rows > 0 && K > 0, who,
+              ": mxfp4 weights need K % 128 == 0 and N % 16 == 0");
+  TORCH_CHECK(Wq.dim() == 2 && Wq.size(0) == rows && Wq.size(1) == K / 2, who, ": Wq must be uint8 [N, K/2]");
+  TORCH_CHECK(scale.numel() == rows * (K / 32), who, ": wscale must be uint8 [N, K/32], one byte per block of 32");
+  TORCH_CHECK(Wq.device() == scale.device(), who, ": Wq and wscale on different devices");
+}
+void shuffle_weight_mxfp4(torch::Tensor Wq, torch::Tensor scale, torch::Tensor W, c10::optional<torch::Tensor> gamma,
+                          int64_t rope_heads, int64_t head_dim, bool swiglu) {
+  check_bf16(W, "W");
+  TORCH_CHECK(W.dim() == 2, "shuffle_weight_mxfp4: W must be [N, K]");
+  check_fp4_weight(Wq, scale, W.size(0), W.size(1), "shuffle_weight_mxfp4");
+  TORCH_CHECK(Wq.device() == W.device(), "shuffle_weight_mxfp4: Wq and W on different devices");
+  const void* gp = nullptr;
+  if (gamma.has_value()) {
+    check_bf16(*gamma, "gamma");
+    TORCH_CHECK(gamma->numel() == W.size(1), "gamma must have K elements");
+    gp = gamma->data_ptr();
+  }
+  const int rc = launch_shuffle_weight_fp4(Wq.data_ptr(), scale.data_ptr<uint8_t>(), W.data_ptr(), gp, (int)W.size(0),
+                                           (int)W.size(1), (int)(rope_heads * head_dim), (int)head_dim,
+                                           swiglu ? 1 : 0, cur_stream());
+  TORCH_CHECK(rc == 0, "shuffle_weight_mxfp4: unsupported configuration (rc=", rc, ")");
+}
+void unshuffle_weight_mxfp4(torch::Tensor W, torch::Tensor Wq, torch::Tensor scale, int64_t rope_heads,
+                            int64_t head_dim, bool swiglu) {
+  check_bf16(W, "W");
+  TORCH_CHECK(W.dim() == 2, "unshuffle_weight_mxfp4: W must be [N, K]");
+  check_fp4_weight(Wq, scale, W.size(0), W.size(1), "unshuffle_weight_mxfp4");
+  TORCH_CHECK(Wq.device() == W.device(), "unshuffle_weight_mxfp4: Wq and W on different devices");
+  const int rc = launch_unshuffle_weight_fp4(W.data_ptr(), Wq.data_ptr(), scale.data_ptr<uint8_t>(), (int)W.size(0),
+                                             (int)W.size(1), (int)(rope_heads * head_dim), (int)head_dim,
+                                             swiglu ? 1 : 0, cur_stream());
+  TORCH_CHECK(rc == 0, "unshuffle_weight_mxfp4: unsupported configuration (rc=", rc, ")");
+}
+// as skinny_gemm_fp8 with e2m1 codes + block scale bytes; M <= 16, pro PLAIN / NORM
+void skinny_gemm_mxfp4(torch::Tensor out, torch::Tensor x, torch::Tensor Wq, torch::Tensor scale, int64_t pro,
+                       int64_t epi, c10::optional<torch::Tensor> res, double eps) {
+  check_bf16(x, "x");
+  TORCH_CHECK(x.dim() == 2, "skinny_gemm_mxfp4: x [M, K]");
+  const int64_t M = x.size(0), K = x.size(1);
+  check_fp4_weight(Wq, scale, Wq.dim() == 2 ? Wq.size(0) : 0, K, "skinny_gemm_mxfp4");
+  TORCH_CHECK(Wq.device() == x.device(), "skinny_gemm_mxfp4: Wq and x on different devices");
+  TORCH_CHECK(M >= 1 && M <= 16, "skinny_gemm_mxfp4: 1 <= M <= 16");
+  TORCH_CHECK(pro == 0 || pro == 1, "skinny_gemm_mxfp4: prologue PLAIN or NORM");
+  TORCH_CHECK(epi >= 0 && epi <= 2, "skinny_gemm_mxfp4: epilogue STORE, RESID or SWIGLU");
+  const GemmOut o = gemm_out("skinny_gemm_mxfp4", out, res, M, Wq.size(0), epi);
+  const int rc = launch_skinny_gemm_fp4(o.out, x.data_ptr(), Wq.data_ptr(), scale.data_ptr<uint8_t>(), o.res, (int)M,
+                                        (int)o.N, (int)K, (int)o.ldo, (float)eps, (int)pro, (int)epi, nullptr,
+                                        cur_stream());
+  TORCH_CHECK(rc == 0, "skinny_gemm_mxfp4: unsupported configuration (rc=", rc, ")");
+}
+void skinny_gemm_rope_mxfp4(torch::Tensor q_out, torch::Tensor x, torch::Tensor Wq, torch::Tensor scale, int64_t pro,
+                            torch::Tensor positions, torch::Tensor cos_sin, torch::Tensor k_cache,
+                            torch::Tensor v_cache, torch::Tensor slots, int64_t Hq, int64_t Hkv, int64_t D, double eps,
+                            c10::optional<torch::Tensor> bias) {
+  check_bf16(q_out, "q_out");
+  check_bf16(x, "x");
+  TORCH_CHECK(x.dim() == 2, "skinny_gemm_rope_mxfp4: x [M, K]");
+  const int64_t M = x.size(0), K = x.size(1);
+  check_fp4_weight(Wq, scale, (Hq + 2 * Hkv) * D, K, "skinny_gemm_rope_mxfp4");
+  TORCH_CHECK(Wq.device() == x.device(), "skinny_gemm_rope_mxfp4: Wq and x on different devices");
+  TORCH_CHECK(M >= 1 && M <= 16, "skinny_gemm_rope_mxfp4: 1 <= M <= 16");
+  TORCH_CHECK(D > 0 && D % 32 == 0,
+              "skinny_gemm_rope_mxfp4: head_dim must be a multiple of 32 (chunk-major K cache layout [D/32][BS][32])");
+  TORCH_CHECK(pro == 0 || pro == 1, "skinny_gemm_rope_mxfp4: prologue PLAIN or NORM");
+  const float* bp = rope_operands("skinny_gemm_rope_mxfp4", q_out, x, M, positions, cos_sin, k_cache, v_cache, slots,
+                                  Hq, Hkv, D, bias);
+  const int rc = launch_skinny_gemm_rope_fp4(q_out.data_ptr(), x.data_ptr(), Wq.data_ptr(), scale.data_ptr<uint8_t>(),
+                                             (int)M, (int)K, (int)pro, (float)eps, positions.data_ptr<int64_t>(),
+                                             cos_sin.data_ptr<float>(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                             slots.data_ptr<int64_t>(), (int)Hq, (int)Hkv, (int)D,
+                                             (int)k_cache.size(2), bp, cur_stream());
+  TORCH_CHECK(rc == 0, "skinny_gemm_rope_mxfp4: unsupported configuration (rc=", rc, ")");
+}
 }  // namespace
 
 PYBIND11_MODULE(_C, m) {
@@ -1019,6 +1109,20 @@ PYBIND11_MODULE(_C, m) {
         py::arg("out"), py::arg("x"), py::arg("Wq"), py::arg("scale"), py::arg("pro"), py::arg("epi"),
         py::arg("res") = py::none(), py::arg("eps") = 1e-5);
   m.def("skinny_gemm_rope_fp8", &skinny_gemm_rope_fp8, "fp8-weight qkv decode GEMM with fused RoPE + K/V cache write",
+        py::arg("q_out"), py::arg("x"), py::arg("Wq"), py::arg("scale"), py::arg("pro"), py::arg("positions"),
+        py::arg("cos_sin"), py::arg("k_cache"), py::arg("v_cache"), py::arg("slots"), py::arg("Hq"), py::arg("Hkv"),
+        py::arg("D"), py::arg("eps") = 1e-5, py::arg("bias") = py::none());
+  m.def("shuffle_weight_mxfp4", &shuffle_weight_mxfp4, "quantise (e2m1 codes, e8m0 block scales) + fragment shuffle",
+        py::arg("Wq"), py::arg("scale"), py::arg("W"), py::arg("gamma") = py::none(), py::arg("rope_heads") = 0,
+        py::arg("head_dim") = 0, py::arg("swiglu") = false);
+  m.def("unshuffle_weight_mxfp4", &unshuffle_weight_mxfp4, "fragment-order codes + block scales -> row-major bf16",
+        py::arg("W"), py::arg("Wq"), py::arg("scale"), py::arg("rope_heads") = 0, py::arg("head_dim") = 0,
+        py::arg("swiglu") = false);
+  m.def("skinny_gemm_mxfp4", &skinny_gemm_mxfp4, "decode GEMM (M<=16) on mxfp4 weights, fused norm / resid / swiglu",
+        py::arg("out"), py::arg("x"), py::arg("Wq"), py::arg("scale"), py::arg("pro"), py::arg("epi"),
+        py::arg("res") = py::none(), py::arg("eps") = 1e-5);
+  m.def("skinny_gemm_rope_mxfp4", &skinny_gemm_rope_mxfp4,
+        "mxfp4-weight qkv decode GEMM with fused RoPE + K/V cache write",
         py::arg("q_out"), py::arg("x"), py::arg("Wq"), py::arg("scale"), py::arg("pro"), py::arg("positions"),
         py::arg("cos_sin"), py::arg("k_cache"), py::arg("v_cache"), py::arg("slots"), py::arg("Hq"), py::arg("Hkv"),
         py::arg("D"), py::arg("eps") = 1e-5, py::arg("bias") = py::none());

@@ -4,7 +4,7 @@
 // shared with the persistent decode-layer kernel; the launch decision (form, variant, geometry)
 // is the pure plan_skinny_gemm of skinny_plan.h. This file holds the kernel wrappers of every
 // form, the (pro, epi) / variant dispatch, the bf16 weight shuffle, and the launchers of both
-// weight types (the fp8 quantiser is gemm_skinny_fp8.hip).
+// weight types (the fp8 quantiser is gemm_skinny_fp8.hip, the mxfp4 one gemm_skinny_fp4.hip).
 //
 // Fusions (details in skinny_core.h):
 //   prologue NORM : RMSNorm with gamma folded into W and 1/rms(x_m) from the same A fragments
@@ -27,7 +27,7 @@ namespace {
 using rt::short8;
 using namespace skinny;
 
-// one tile per workgroup; WT_FP8: e4m3 weight codes, dequantised in registers (skinny_core.h)
+// one tile per workgroup; WT_FP8 / WT_FP4: e4m3 / e2m1 weight codes, dequantised in registers (skinny_core.h)
 template <int PRO, int EPI, int NW, int U, int WT = WT_BF16>
 __global__ void __launch_bounds__(NW * 64) skinny_gemm_kernel(GemmArgs p) {
   __shared__ GemmSmem<nacc<EPI>(), NW> sm;
@@ -203,6 +203,8 @@ int launch_plan(const SkinnyPlan& pl, const GemmArgs& args, int pro, int epi, in
         const auto go = [&](auto v) { return launch(skinny_gemm_kernel<P(), E(), v.NW, v.U, WT>, pl, stream, args); };
         if constexpr (WT == WT_FP8)
           return with_variant<V<4, 2>, V<4, 4>>(pl, go);
+        else if constexpr (WT == WT_FP4)
+          return with_variant<V<4, 1>, V<4, 2>>(pl, go);
         else
           return with_variant<V<4, 2>, V<16, 2>, V<8, 2>, V<4, 8>, V<8, 4>, V<8, 8>, V<4, 4>>(pl, go);
       });
@@ -239,14 +241,17 @@ int launch_plan(const SkinnyPlan& pl, const GemmArgs& args, int pro, int epi, in
 }
 
 // validate -> plan -> fill GemmArgs -> one dispatch on the plan's form. WT_FP8: Ws holds fp8 weight
-// codes and wscale their per-row scales (M <= 16, K % 64 == 0); N = output columns (SwiGLU: I).
-int launch_gemm(int wt, void* out, const void* x, const void* Ws, const float* wscale, void* res, int M, int N, int K,
+// codes and wscale their per-row fp32 scales (M <= 16, K % 64 == 0); WT_FP4: Ws holds e2m1 codes and
+// wscale their e8m0 block scale bytes in record order (M <= 16, K % 128 == 0); N = output columns
+// (SwiGLU: I).
+int launch_gemm(int wt, void* out, const void* x, const void* Ws, const void* wscale, void* res, int M, int N, int K,
                 int ldo, float eps, int pro, int epi, const void* rope, const void* x2, void* xo, hipStream_t stream,
                 int* split_ws, int64_t split_ws_ints, int split_mode) {
-  const bool f8 = wt == WT_FP8;
+  const bool f8 = wt != WT_BF16;   // quantised weights, either type
+  const int kd = wt == WT_FP4 ? kdeep<WT_FP4>() : (wt == WT_FP8 ? kdeep<WT_FP8>() : kdeep<WT_BF16>());
   if (!f8 && pro == PRO_NORM_ADD && x2 == nullptr) return -5;
   // 17..32 rows: only the multi-tile launches (two 16-row blocks per MFMA pass)
-  if (M < 1 || M > (f8 ? 16 : 32) || K <= 0 || N <= 0 || K % (f8 ? 64 : 32) || N % 16 || (f8 && wscale == nullptr))
+  if (M < 1 || M > (f8 ? 16 : 32) || K <= 0 || N <= 0 || K % kd || N % 16 || (f8 && wscale == nullptr))
     return -1;
   if (M > 16 && (pro == PRO_NORM_ADD || epi == EPI_AR)) return -1;
   if (f8 && pro != PRO_PLAIN && pro != PRO_NORM) return -2;   // reported ahead of a missing ROPE operand
@@ -263,7 +268,11 @@ int launch_gemm(int wt, void* out, const void* x, const void* Ws, const float* w
   GemmArgs args{(uint16_t*)out, (const uint16_t*)x, (const short8*)Ws, (uint16_t*)res, M, N, K, ldo,
                 eps, re, (const uint16_t*)x2, (uint16_t*)xo};
   args.kmajor = resolve_order(N / 16, K, epi == EPI_SWIGLU, epi == EPI_ROPE);
-  args.wscale = wscale;
+  if (wt == WT_FP4) {
+    args.bscale = static_cast<const uint8_t*>(wscale);
+    return launch_plan<WT_FP4>(pl, args, pro, epi, split_ws, stream);
+  }
+  args.wscale = static_cast<const float*>(wscale);
   return f8 ? launch_plan<WT_FP8>(pl, args, pro, epi, split_ws, stream)
             : launch_plan<WT_BF16>(pl, args, pro, epi, split_ws, stream);
 }
@@ -330,6 +339,23 @@ int launch_skinny_gemm_rope_fp8(void* q_out, const void* x, const void* Wq, cons
                                 const float* bias, hipStream_t stream) {
   const RopeEpi re{positions, cos_sin, (uint16_t*)k_cache, (uint16_t*)v_cache, slots, Hq, Hkv, D, BS, bias};
   return launch_skinny_gemm_fp8(q_out, x, Wq, scale, nullptr, M, (Hq + 2 * Hkv) * D, K, 0, eps, pro, EPI_ROPE, &re,
+                                stream);
+}
+
+// mxfp4 weights (Wq, scale: gemm_skinny_fp4.hip): as the fp8 launches, with one scale BYTE per
+// lane record (block of 32 k) instead of one float per row
+int launch_skinny_gemm_fp4(void* out, const void* x, const void* Wq, const uint8_t* scale, void* res, int M, int N,
+                           int K, int ldo, float eps, int pro, int epi, const void* rope, hipStream_t stream) {
+  return launch_gemm(WT_FP4, out, x, Wq, scale, res, M, N, K, ldo, eps, pro, epi, rope, nullptr, nullptr, stream,
+                     nullptr, 0, 0);
+}
+
+int launch_skinny_gemm_rope_fp4(void* q_out, const void* x, const void* Wq, const uint8_t* scale, int M, int K,
+                                int pro, float eps, const int64_t* positions, const float* cos_sin, void* k_cache,
+                                void* v_cache, const int64_t* slots, int Hq, int Hkv, int D, int BS,
+                                const float* bias, hipStream_t stream) {
+  const RopeEpi re{positions, cos_sin, (uint16_t*)k_cache, (uint16_t*)v_cache, slots, Hq, Hkv, D, BS, bias};
+  return launch_skinny_gemm_fp4(q_out, x, Wq, scale, nullptr, M, (Hq + 2 * Hkv) * D, K, 0, eps, pro, EPI_ROPE, &re,
                                 stream);
 }
 

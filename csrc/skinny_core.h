@@ -36,6 +36,20 @@
 // (weight_order), with the chunks covering the same k range (half the records). scale[n] is
 // indexed by the epilogue's own column (ROPE: pair-interleaved rows; SwiGLU: gate rows [0, I),
 // up rows [I, 2I)) and multiplies the finished fp32 column sum after the 1/rms factor.
+//
+// MXFP4 weights (WT = WT_FP4, built by `shuffle_weight_mxfp4` in gemm_skinny_fp4.hip, launched from
+// gemm_skinny.hip): OCP e2m1 codes, two per byte (low nibble first), with one e8m0 scale byte per
+// block of 32 consecutive k of a row (fp4_core.h). A record is again 64 lanes x 16 B = 1 KiB, now
+// 128 deep in k: a lane holds 32 CONSECUTIVE k of its row, exactly one scaled block,
+//     Wq[N/16][K/128][64 lanes][16]  with byte j of Wq[t][s][l] = codes of W[16t + (l&15)][128s + 32(l>>4) + 2j, +1]
+// (SwiGLU paired as above). A k-step is one record = four MFMAs: dword q (q = 0..3) of the lane's
+// 16 bytes becomes the bf16 B fragment through four v_cvt_scalef32_pk_bf16_fp4, which apply the
+// block's scale 2^(e-127) in the convert (exact: every product is a bf16 value), against the A
+// fragment x[m][128s + 32(l>>4) + 8q ..+8). The scale bytes are a second array in RECORD ORDER:
+// the scale of lane record r (lane_record().rec) is byte r, so a wave reads 64 contiguous bytes
+// per record (128 for SwiGLU) at the offset of its weight load. No per-row scale, no multiply in
+// the epilogue: the epilogues are the bf16 ones. Chunked record orders cover the bf16 order's k
+// range (a quarter of the records; k-major stays one record).
 #pragma once
 #include "common.h"
 
@@ -46,10 +60,10 @@ using rt::short8;
 
 enum : int { PRO_PLAIN = 0, PRO_NORM = 1, PRO_NORM_ADD = 2 };
 enum : int { EPI_STORE = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_ROPE = 3, EPI_AR = 4 };
-enum : int { WT_BF16 = 0, WT_FP8 = 1 };   // weight element type (header: FP8 weights)
+enum : int { WT_BF16 = 0, WT_FP8 = 1, WT_FP4 = 2 };   // weight element type (header: FP8 / MXFP4 weights)
 // MFMAs (32-deep A fragments) per weight record, k elements per record
 template <int WT>
-constexpr int kfrag() { return WT == WT_FP8 ? 2 : 1; }
+constexpr int kfrag() { return WT == WT_FP4 ? 4 : (WT == WT_FP8 ? 2 : 1); }
 template <int WT>
 constexpr int kdeep() { return 32 * kfrag<WT>(); }
 
@@ -92,6 +106,7 @@ struct GemmArgs {
   int kmajor = -1;
   ArEpi ar{};           // EPI_AR only
   const float* wscale = nullptr;   // WT_FP8: per-row weight scales in the epilogue's column order
+  const uint8_t* bscale = nullptr; // WT_FP4: one e8m0 scale byte per lane record, in record order
 };
 
 template <int NACC, int NW>   // NACC = accumulators per lane (2 for SwiGLU gate + up)
@@ -160,6 +175,15 @@ RT_DEVICE short8 ld_x8(const XSrc& x, int elem) {
     return *reinterpret_cast<const short8*>(x.base + elem);
 }
 
+// the block scale bytes that travel with a stage's MXFP4 records (empty for the other types)
+template <int EPI, int U, int WT>
+struct StageScale {};
+template <int EPI, int U>
+struct StageScale<EPI, U, WT_FP4> {
+  unsigned e[U];
+  unsigned e2[(EPI == EPI_SWIGLU) ? U : 1];
+};
+
 // U = k-steps per wave per pipeline stage (x2 stages in flight)
 template <int PRO, int EPI, int U, int WT = WT_BF16>
 struct Stage {
@@ -167,6 +191,7 @@ struct Stage {
   short8 w2[(EPI == EPI_SWIGLU) ? U : 1];
   short8 a[U * kfrag<WT>()];
   short8 b[(PRO == PRO_NORM_ADD) ? U : 1];
+  StageScale<EPI, U, WT> sc;
 };
 
 // short8 records per k-step of one tile (SwiGLU: gate + up)
@@ -196,11 +221,13 @@ __host__ __device__ inline int weight_order(int tiles, int K, bool swiglu, bool 
   return order;
 }
 
-// log2(records per chunk) of `order` > 0 for weight type WT. FP8: the chunks cover the same k
-// range as the bf16 weight's, i.e. half as many 64-deep records (k-major stays one record)
+// log2(records per chunk) of `order` > 0 for weight type WT. FP8 / MXFP4: the chunks cover the
+// same k range as the bf16 weight's, i.e. a half / a quarter as many 64- / 128-deep records
+// (k-major stays one record)
 template <int WT>
 __host__ __device__ inline int chunk_log2(int order) {
-  return WT == WT_FP8 ? (order >= 2 ? order - 2 : 0) : order - 1;
+  constexpr int lf = WT == WT_FP4 ? 2 : (WT == WT_FP8 ? 1 : 0);   // log2(kfrag)
+  return order - 1 >= lf ? order - 1 - lf : 0;
 }
 // index of the first record of (tile t, k-step s) in a layout of T tiles x ks steps (s, ks in
 // records of kdeep<WT>() k elements)
@@ -228,10 +255,10 @@ __host__ __device__ inline int source_row(int row, int rope_rows, int D) {
 // The shuffle / quantise kernels write W[src][k0..] to Ws[rec], the unshuffle / dequantise
 // kernels read it back, and the GEMMs (tile_base) walk the same order.
 struct LaneRec {
-  int orow;    // row in the epilogue's order (indexes the fp8 scales)
+  int orow;    // row in the epilogue's order (indexes the fp8 row scales)
   int src;     // row of the row-major weight (ROPE rows pair-interleaved)
   int k0;      // first k of the record's kdeep/4 consecutive elements
-  size_t rec;  // offset in 16-byte records
+  size_t rec;  // offset in 16-byte records (and of the record's MXFP4 scale byte)
 };
 template <int WT>
 __host__ __device__ inline int64_t lane_records(int N, int K) {
@@ -269,7 +296,7 @@ struct WStride {
 
 template <int PRO, int EPI, int NW, int U, int WT = WT_BF16>
 RT_DEVICE void issue_w(Stage<PRO, EPI, U, WT>& st, const short8* __restrict__ wt, const short8* __restrict__ wt2, int s0,
-                       int nsteps, int lane, WStride ws) {
+                       int nsteps, int lane, WStride ws, const uint8_t* __restrict__ bs = nullptr) {
   // SwiGLU weights are stored k-step-paired ([tile][step][gate|up][64 lanes][8]): one wave streams
   // 2 KiB contiguous per step instead of two 1-KiB streams 117 MB apart (`wt2` unused)
 #pragma unroll
@@ -280,6 +307,11 @@ RT_DEVICE void issue_w(Stage<PRO, EPI, U, WT>& st, const short8* __restrict__ wt
     const size_t o = ws.off(s, krec<EPI>());
     st.w[u] = __builtin_nontemporal_load(wt + o + lane);
     if constexpr (EPI == EPI_SWIGLU) st.w2[u] = __builtin_nontemporal_load(wt + o + 64 + lane);
+    if constexpr (WT == WT_FP4) {
+      // `bs` = the tile's first scale byte: one byte per lane record, at the record's own offset
+      st.sc.e[u] = __builtin_nontemporal_load(bs + o + lane);
+      if constexpr (EPI == EPI_SWIGLU) st.sc.e2[u] = __builtin_nontemporal_load(bs + o + 64 + lane);
+    }
   }
 }
 
@@ -308,10 +340,11 @@ RT_DEVICE void issue_a(Stage<PRO, EPI, U, WT>& st, const XSrc& xr, const XSrc& x
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const int s = min(s0 + NW * u, nsteps - 1);
-    if constexpr (WT == WT_FP8) {
-      // the lane's 16 consecutive k of the record: two A fragments, 32 B contiguous
-      st.a[2 * u] = ld_x8<SC1>(xr, s * 64);
-      st.a[2 * u + 1] = ld_x8<SC1>(xr, s * 64 + 8);
+    if constexpr (WT != WT_BF16) {
+      // the lane's 16 (fp8) / 32 (fp4) consecutive k of the record: two / four A fragments,
+      // 32 / 64 B contiguous
+#pragma unroll
+      for (int q = 0; q < kfrag<WT>(); ++q) st.a[kfrag<WT>() * u + q] = ld_x8<SC1>(xr, s * kdeep<WT>() + 8 * q);
     } else {
       st.a[u] = ld_x8<SC1>(xr, s * 32);
     }
@@ -333,21 +366,41 @@ RT_DEVICE bf16x8 fp8_frag(const short8& w, int q) {
   return bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
 }
 
+// dword q (0..3) of an MXFP4 record lane (8 e2m1 codes, low nibble first) as a bf16 MFMA fragment
+// under the block's scale byte e: the scale operand is the float 2^(e-127) = e << 23, applied in
+// the convert (one v_cvt_scalef32_pk_bf16_fp4 per byte, byte select = op_sel), exact
+RT_DEVICE bf16x8 fp4_frag(const short8& w, int q, unsigned e) {
+  const u32x4_ c = __builtin_bit_cast(u32x4_, w);
+  const unsigned d = q == 0 ? c[0] : (q == 1 ? c[1] : (q == 2 ? c[2] : c[3]));
+  const float sc = __builtin_bit_cast(float, e << 23);
+  const bf16x2_ p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 0);
+  const bf16x2_ p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 1);
+  const bf16x2_ p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 2);
+  const bf16x2_ p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 3);
+  return bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+}
+
 template <int PRO, int EPI, int NW, int U, bool SC1, int WT = WT_BF16>
 RT_DEVICE void consume(const Stage<PRO, EPI, U, WT>& st, float4_& acc, float4_& acc2, float& ssq, int s0, int nsteps,
                        uint16_t* __restrict__ xo_r, const XSrc& xo_s) {
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     if (s0 + NW * u < nsteps) {
-      if constexpr (WT == WT_FP8) {
-        static_assert(PRO != PRO_NORM_ADD, "fp8 weights: plain / norm prologues");
+      if constexpr (WT != WT_BF16) {
+        static_assert(PRO != PRO_NORM_ADD, "fp8 / mxfp4 weights: plain / norm prologues");
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const short8 aq = st.a[2 * u + q];
+        for (int q = 0; q < kfrag<WT>(); ++q) {
+          const short8 aq = st.a[kfrag<WT>() * u + q];
           const bf16x8 a = __builtin_bit_cast(bf16x8, aq);
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, fp8_frag(st.w[u], q), acc, 0, 0, 0);
-          if constexpr (EPI == EPI_SWIGLU)
-            acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, fp8_frag(st.w2[u], q), acc2, 0, 0, 0);
+          if constexpr (WT == WT_FP4) {
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, fp4_frag(st.w[u], q, st.sc.e[u]), acc, 0, 0, 0);
+            if constexpr (EPI == EPI_SWIGLU)
+              acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, fp4_frag(st.w2[u], q, st.sc.e2[u]), acc2, 0, 0, 0);
+          } else {
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, fp8_frag(st.w[u], q), acc, 0, 0, 0);
+            if constexpr (EPI == EPI_SWIGLU)
+              acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, fp8_frag(st.w2[u], q), acc2, 0, 0, 0);
+          }
           if constexpr (PRO != PRO_PLAIN) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -625,7 +678,7 @@ RT_DEVICE void gemm_tile(const GemmArgs& p, int tile, GemmSmem<nacc<EPI>(), NW>&
   constexpr bool SC1A = AC < 0 ? SC1 : AC != 0;
   static_assert(!(ALDS && SC1 && AC < 0), "an LDS-staged A operand in a persistent launch needs an explicit AC");
   static_assert(WT == WT_BF16 || (!ALDS && !SC1 && PRO != PRO_NORM_ADD && EPI != EPI_AR),
-                "fp8 weights: one launch per GEMM, plain / norm prologues, no LDS-staged A, no all-reduce");
+                "fp8 / mxfp4 weights: one launch per GEMM, plain / norm prologues, no LDS-staged A, no all-reduce");
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 15, g = lane >> 4;
   const int M = p.M, N = p.N, K = p.K;
@@ -644,6 +697,9 @@ RT_DEVICE void gemm_tile(const GemmArgs& p, int tile, GemmSmem<nacc<EPI>(), NW>&
   WStride sstride;
   const short8* wt = tile_base<EPI, WT>(p, tile, sstride);
   const short8* wt2 = nullptr;
+  // mxfp4: the tile's first scale byte (record order: the same offsets as the weight records)
+  const uint8_t* bs = nullptr;
+  if constexpr (WT == WT_FP4) bs = p.bscale + (wt - p.Ws);
 
   float4_ acc = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f};
   float ssq = 0.f;
@@ -654,7 +710,7 @@ RT_DEVICE void gemm_tile(const GemmArgs& p, int tile, GemmSmem<nacc<EPI>(), NW>&
   constexpr int SPAN = NW * U;
   const int w0 = s_lo + wid;   // this wave's first k-step
   const int nst = w0 < nsteps ? (nsteps - w0 + SPAN - 1) / SPAN : 0;
-  if (!prefetched) issue_w<PRO, EPI, NW, U, WT>(st0, wt, wt2, w0, nsteps, lane, sstride);
+  if (!prefetched) issue_w<PRO, EPI, NW, U, WT>(st0, wt, wt2, w0, nsteps, lane, sstride, bs);
   const uint16_t* arow = nullptr;
   if constexpr (ALDS) {
     // stage-0 weights are in flight; stage A once (its loads overlap theirs), then the k-loop
@@ -706,10 +762,10 @@ RT_DEVICE void gemm_tile(const GemmArgs& p, int tile, GemmSmem<nacc<EPI>(), NW>&
   } else {
     for (; j + 1 < nst; j += 2) {
       const int s = w0 + SPAN * j;
-      issue_w<PRO, EPI, NW, U, WT>(st1, wt, wt2, s + SPAN, nsteps, lane, sstride);
+      issue_w<PRO, EPI, NW, U, WT>(st1, wt, wt2, s + SPAN, nsteps, lane, sstride, bs);
       issue_a<PRO, EPI, NW, U, SC1A, WT>(st1, xr, xr2, row_ok, s + SPAN, nsteps);
       consume<PRO, EPI, NW, U, SC1A, WT>(st0, acc, acc2, ssq, s, nsteps, xo_r, xo_s);
-      issue_w<PRO, EPI, NW, U, WT>(st0, wt, wt2, s + 2 * SPAN, nsteps, lane, sstride);
+      issue_w<PRO, EPI, NW, U, WT>(st0, wt, wt2, s + 2 * SPAN, nsteps, lane, sstride, bs);
       issue_a<PRO, EPI, NW, U, SC1A, WT>(st0, xr, xr2, row_ok, s + 2 * SPAN, nsteps);
       consume<PRO, EPI, NW, U, SC1A, WT>(st1, acc, acc2, ssq, s + SPAN, nsteps, xo_r, xo_s);
     }

@@ -95,10 +95,10 @@ enum Form : int { ONE_TILE, ALDS, SPLITK, MULTI, MULTI_SPLIT, BALANCED };
 // The (pro, epi) pairs each form launches. bf16 one-tile, ALDS and split-K carry the three
 // NORM_ADD pairs and no (NORM, RESID); the serving-batch forms take PLAIN / NORM with every
 // epilogue; the CU-balanced form is not for NORM_ADD (its workgroup 0 publishes the whole K
-// row). fp8 weights: one tile, PLAIN / NORM, every epilogue.
+// row). fp8 and mxfp4 weights: one tile, PLAIN / NORM, every epilogue.
 constexpr bool allowed(int form, int wt, int pro, int epi) {
   if (pro < PRO_PLAIN || pro > PRO_NORM_ADD || epi < EPI_STORE || epi > EPI_ROPE) return false;
-  if (wt == WT_FP8) return form == ONE_TILE && pro != PRO_NORM_ADD;
+  if (wt != WT_BF16) return form == ONE_TILE && pro != PRO_NORM_ADD;
   if (form == MULTI || form == MULTI_SPLIT) return pro != PRO_NORM_ADD;
   if (epi == EPI_RESID) return pro == PRO_PLAIN;
   return form != BALANCED || pro != PRO_NORM_ADD;
@@ -154,7 +154,7 @@ inline int splitk_parts(int T, int ks, int cus, int64_t ws_ints, const SkinnyKno
   return S >= 2 ? S : 0;
 }
 
-// The launch of one validated decode GEMM: N = output columns (SwiGLU: I), M <= 32 (fp8: 16).
+// The launch of one validated decode GEMM: N = output columns (SwiGLU: I), M <= 32 (fp8, mxfp4: 16).
 // `have_split_ws` / `split_ws_ints`: the caller's split workspace; split_mode bit 0 allows the
 // CU-balanced form, bit 1 split-K.
 inline SkinnyPlan plan_skinny_gemm(int wt, int M, int N, int K, int pro, int epi, int cus, bool have_split_ws,
@@ -173,6 +173,11 @@ inline SkinnyPlan plan_skinny_gemm(int wt, int M, int N, int K, int pro, int epi
   // fp8 weights: one tile per workgroup; (waves, records per stage) as the bf16 launch of the
   // same shape: the same weight bytes in flight per workgroup
   if (wt == WT_FP8) return done(ONE_TILE, T >= 384 ? 402 : 404, T);
+  // mxfp4 weights: one tile per workgroup. A 128-deep record brings four activation fragments, so
+  // the fp8 launch's k range per stage is half its record count: 4 waves x 1 record for the wide
+  // GEMMs, x 2 for the rest (the same activation bytes in flight as fp8, half the weight bytes).
+  // The first form only: not tuned
+  if (wt == WT_FP4) return done(ONE_TILE, T >= 384 ? 401 : 402, T);
   // split-K (split_mode bit 1) when the shape has fewer tiles than CUs: tensor-parallel shards
   if (have_split_ws && (split_mode & 2) && M <= 16) {
     const int S = splitk_parts(T, K / 32, cus, split_ws_ints, kn);

@@ -777,9 +777,9 @@ def build_parser() -> argparse.ArgumentParser:
     sv.add_argument("--weights", default="random:0", help="random:<seed> | random-full:<seed> | <safetensors dir>")
     sv.add_argument("--device", default="cuda:0")
     sv.add_argument("--dtype", default="bf16")
-    sv.add_argument("--weight-quant", dest="weight_quant", choices=["none", "fp8"], default=None,
-                    help="weight-only quantisation of the decode linears (fp8: e4m3 codes + per-row scales, "
-                         "tp 1, bf16 activations); default: ROUNDTABLE_WEIGHT_QUANT or none")
+    sv.add_argument("--weight-quant", dest="weight_quant", choices=["none", "fp8", "mxfp4"], default=None,
+                    help="weight-only quantisation of the decode linears (fp8: e4m3 codes + per-row scales; "
+                         "mxfp4: e2m1 codes + one scale byte per 32 weights; tp 1, bf16 activations); default: ROUNDTABLE_WEIGHT_QUANT or none")
     sv.add_argument("--host", default="127.0.0.1")
     sv.add_argument("--port", type=int, default=8000)
     sv.add_argument("--max-batch", type=int, default=None,

@@ -119,11 +119,11 @@ def validate_config(cfg: Dict[str, Any]) -> None:
         raise ConfigError("config.json missing 'adapter_config' section.")
 
 
-WEIGHT_QUANTS = ("none", "fp8")
+WEIGHT_QUANTS = ("none", "fp8", "mxfp4")
 
 
 def resolve_weight_quant(value: Optional[str]) -> str:
-    """A stated ``weight_quant`` ("none" | "fp8"), or — when a config says nothing (None / "") —
+    """A stated ``weight_quant`` ("none" | "fp8" | "mxfp4"), or — when a config says nothing (None / "") —
     the ROUNDTABLE_WEIGHT_QUANT default, else "none"."""
     q = str(value if value else os.environ.get("ROUNDTABLE_WEIGHT_QUANT") or "none").lower()
     if q not in WEIGHT_QUANTS:
@@ -133,7 +133,7 @@ def resolve_weight_quant(value: Optional[str]) -> str:
 
 def engine_settings(config: RoundtableConfig, adapter_id: str) -> Dict[str, Any]:
     """Effective engine settings for one adapter id: defaults <- config.engine <- adapter engine.
-    ``weight_quant`` (engine-wide or per knight) comes back resolved: "none" | "fp8".
+    ``weight_quant`` (engine-wide or per knight) comes back resolved: "none" | "fp8" | "mxfp4".
     ``consensus_grammar`` (engine-wide or per knight) is a bool; with ``scripted_consensus`` a ConfigError."""
     out = dict(ENGINE_DEFAULTS)
     top = config.raw.get("engine") if isinstance(config.raw, dict) else None

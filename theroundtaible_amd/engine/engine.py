@@ -77,9 +77,11 @@ class EngineConfig:
     # GPU weight copies: "dual" (row-major for prefill + shuffled for decode), "shuffled" (shuffled
     # only; prefill unshuffles per GEMM into scratch), "auto" = dual when 2x weights <= 35% of HBM
     weight_residency: str = "auto"
-    # weight-only quantisation of the decode linears: "none" | "fp8" (OCP e4m3fn codes + one fp32
+    # weight-only quantisation of the decode linears: "none" | "fp8" | "mxfp4" (fp8: OCP e4m3fn codes + one fp32
     # scale per weight row, bf16 activations; csrc/gemm_skinny_fp8.hip). "fp8" keeps ONE copy (the
     # codes) resident — ``weight_residency`` becomes "fp8" — and the KV pool is sized after it.
+    # "mxfp4": OCP e2m1 codes + one e8m0 scale byte per 32 consecutive k (17/32 byte per weight;
+    # csrc/gemm_skinny_fp4.hip), every semantic of "fp8" (``weight_residency`` "mxfp4").
     # Default: "none", or ROUNDTABLE_WEIGHT_QUANT when the caller states nothing
     weight_quant: str = field(default_factory=lambda: resolve_weight_quant(None))
 
@@ -122,31 +124,32 @@ class Engine:
         if not self.on_gpu and self.dtype == torch.float16:
             self.dtype = torch.float32
         self.weight_quant = resolve_weight_quant(ecfg.weight_quant)
-        if self.weight_quant == "fp8":
+        wq = self.weight_quant
+        if wq != "none":
             # refuse before any weight is loaded: never a silent bf16 run
             if self.tp.size > 1:
-                raise ConfigError(f"{ecfg.model}: weight_quant='fp8' does not support tensor parallel "
+                raise ConfigError(f"{ecfg.model}: weight_quant={wq!r} does not support tensor parallel "
                                   f"(tp={self.tp.size})", hint="Run the knight at tp 1 or drop weight_quant.")
             if self.on_gpu and self.dtype != torch.bfloat16:
-                raise ConfigError(f"{ecfg.model}: weight_quant='fp8' needs dtype bf16 on the GPU (got {ecfg.dtype})")
+                raise ConfigError(f"{ecfg.model}: weight_quant={wq!r} needs dtype bf16 on the GPU (got {ecfg.dtype})")
         # the checkpoint's own tokenizer + chat template when `weights` ships one, else the bundled BPE
         self.tokenizer: EngineTokenizer = get_tokenizer(self.cfg.vocab, ecfg.weights, ecfg.chat_template)
         t0 = time.perf_counter()
         with torch.no_grad():
             weights = materialize(self.cfg, ecfg.weights, self.device, self.dtype, self.tp)
             self.model = build_model(self.cfg, weights, self.device, self.dtype, self.tp)
-            if self.weight_quant == "fp8":
+            if wq != "none":
                 if not hasattr(self.model, "decode_weights"):
-                    raise ConfigError(f"{ecfg.model}: weight_quant='fp8' needs a model family with fused decode "
+                    raise ConfigError(f"{ecfg.model}: weight_quant={wq!r} needs a model family with fused decode "
                                       f"weights (Llama / Mistral / Qwen2), not {self.cfg.arch}")
-                err = self.model.fp8_width_error()
+                err = self.model.quant_width_error(wq)
                 if err:
-                    raise ConfigError(f"{ecfg.model}: weight_quant='fp8': {err}")
+                    raise ConfigError(f"{ecfg.model}: weight_quant={wq!r}: {err}")
                 # quantise one linear at a time, freeing its row-major tensor (load peak: one bf16
                 # copy + one tensor); the KV pool below is sized from what is then free
                 del weights
-                self.model.decode_weights(quant="fp8")
-                self.weight_residency = "fp8"
+                self.model.decode_weights(quant=wq)
+                self.weight_residency = wq
             elif self.on_gpu and hasattr(self.model, "decode_weights"):
                 # shuffled decode copies before sizing the KV pool. Both layouts (+1x weight memory)
                 # when that leaves most of HBM to KV; otherwise shuffle in place and keep ONLY the

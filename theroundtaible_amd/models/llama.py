@@ -85,12 +85,12 @@ class LlamaModel:
         cfg = self.cfg
         rows = 32 if self.tp.size == 1 and not self.force_tp_path else 16
         rows = min(rows, int(os.environ.get("ROUNDTABLE_FUSED_ROWS", rows)))   # A/B knob
-        if self.quant == "fp8":
+        if self.quant in ("fp8", "mxfp4"):
             # tp 1 only, <= 32 rows (two launches of 16); more rows take the unfused path on
             # operands dequantised into scratch (correct, slow)
             if self.tp.size != 1 or self.force_tp_path:
                 return False
-            rows = min(rows, ops.FP8_MAX_ROWS)
+            rows = min(rows, ops.FP8_MAX_ROWS if self.quant == "fp8" else ops.MXFP4_MAX_ROWS)
         return (ids.is_cuda and 1 <= ids.shape[0] <= rows and self.use_fused
                 and cfg.hidden % 32 == 0 and cfg.ffn % 32 == 0 and (cfg.n_heads * cfg.head_dim) % 32 == 0
                 and self.lm_rows % 16 == 0)
@@ -105,21 +105,28 @@ class LlamaModel:
     shuffled_only = False
     _scratch: Optional[Dict[tuple, torch.Tensor]] = None
     # weight quantisation of the decode linears: None | "fp8" (e4m3fn codes + per-row scales,
-    # csrc/gemm_skinny_fp8.hip). Always single-copy: the dequantised row-major operand of the
+    # csrc/gemm_skinny_fp8.hip) | "mxfp4" (e2m1 codes + one e8m0 scale byte per 32 k,
+    # csrc/gemm_skinny_fp4.hip). Always single-copy: the dequantised row-major operand of the
     # prefill / unfused GEMMs is rebuilt in the same scratch as shuffled-only residency, so every
     # path computes with the SAME weights bf16(code * scale)
     quant: Optional[str] = None
 
-    def fp8_width_error(self) -> Optional[str]:
-        """Why this model's GEMM depths do not fit the fp8 k-record (None: they fit)."""
+    def quant_width_error(self, quant: str) -> Optional[str]:
+        """Why this model's GEMM depths do not fit the k-record of ``quant`` ("fp8": 64 deep,
+        "mxfp4": 128 deep) (None: they fit)."""
         cfg = self.cfg
+        record = ops.MXFP4_K_RECORD if quant == "mxfp4" else ops.FP8_K_RECORD
         for what, k in (("hidden", cfg.hidden), ("ffn / tp", cfg.ffn // self.tp.size),
                         ("heads x head_dim / tp", self.n_heads * self.head_dim)):
-            if k % ops.FP8_K_RECORD:
-                return f"{what} = {k} is not a multiple of the fp8 k-record ({ops.FP8_K_RECORD})"
+            if k % record:
+                return f"{what} = {k} is not a multiple of the {quant} k-record ({record})"
         if self.lm_rows % 16:
             return f"lm_head rows = {self.lm_rows} is not a multiple of 16"
         return None
+
+    def fp8_width_error(self) -> Optional[str]:
+        """Why this model's GEMM depths do not fit the fp8 k-record (None: they fit)."""
+        return self.quant_width_error("fp8")
 
     # (name, folded norm, shuffle kwargs) of the linears the fused decode path streams
     def _lin_specs(self):
@@ -132,21 +139,24 @@ class LlamaModel:
         ``drop_originals``: shuffle one linear at a time and free its row-major tensor (peak +1
         tensor), so only ONE copy of the weights stays resident (see :attr:`shuffled_only`).
         ``quant="fp8"``: quantise each linear instead (``name`` -> uint8 codes, ``name_scale`` ->
-        fp32 row scales); always drops the originals. The embedding table stays bf16 (a tied
-        lm_head loses only its own reference)."""
+        fp32 row scales); ``quant="mxfp4"``: ``name`` -> uint8 e2m1 codes ``[N, K/2]``,
+        ``name_scale`` -> uint8 block scale bytes ``[N, K/32]``. Both always drop the originals. The
+        embedding table stays bf16 (a tied lm_head loses only its own reference)."""
         if self._dec is None:
-            if quant not in (None, "none", "fp8"):
+            if quant not in (None, "none", "fp8", "mxfp4"):
                 raise ValueError(f"unknown weight quantisation {quant!r}")
-            fp8 = quant == "fp8"
+            fp8 = quant in ("fp8", "mxfp4")   # quantised, either type: one copy, no split workspace
             if fp8:
-                err = self.fp8_width_error()
+                err = self.quant_width_error(quant)
                 if err or self.tp.size != 1:
-                    raise ValueError(f"{self.cfg.name}: fp8 weights: {err or 'tensor parallel is not supported'}")
+                    raise ValueError(f"{self.cfg.name}: {quant} weights: {err or 'tensor parallel is not supported'}")
                 drop_originals = True
-                self.quant = "fp8"
+                self.quant = quant
 
             def shuffle(W, gamma, d, name, **kw):
-                if fp8:
+                if quant == "mxfp4":
+                    d[name], d[name + "_scale"] = ops.shuffle_weight_mxfp4(W, gamma, **kw)
+                elif fp8:
                     d[name], d[name + "_scale"] = ops.shuffle_weight_fp8(W, gamma, **kw)
                 else:
                     d[name] = ops.shuffle_weight(W, gamma, **kw)
@@ -182,7 +192,7 @@ class LlamaModel:
                 # the engine's stream; counters re-arm at the end of each call): split-K for shard
                 # shapes with fewer tiles than CUs (tensor parallel), and the balanced launch of
                 # gate_up, whose tile count (ffn/16) is rarely a multiple of the CU count
-                # (the fp8 launches have no split forms: no workspace)
+                # (the fp8 / mxfp4 launches have no split forms: no workspace)
                 ws = ops.split_workspace(lm.device) if lm.is_cuda and not fp8 else None
                 self._dec = {"layers": layers, "split_ws": ws, **top}
         return self._dec
@@ -198,10 +208,13 @@ class LlamaModel:
             d = self._dec["layers"][l]
             kw = next(k for n, _, k in self._lin_specs() if n == name)
         Ws = d[name]
-        key = tuple(Ws.shape)
+        # (mxfp4 codes hold two k per byte: the operand is [N, K], not the codes' [N, K/2])
+        key = (Ws.shape[0], 2 * Ws.shape[1]) if self.quant == "mxfp4" else tuple(Ws.shape)
         buf = self._scratch.get(key)
         if buf is None:
-            buf = self._scratch[key] = torch.empty(Ws.shape, dtype=self.dtype, device=Ws.device)
+            buf = self._scratch[key] = torch.empty(key, dtype=self.dtype, device=Ws.device)
+        if self.quant == "mxfp4":
+            return ops.unshuffle_weight_mxfp4(Ws, d[name + "_scale"], out=buf, **kw)
         if self.quant == "fp8":
             return ops.unshuffle_weight_fp8(Ws, d[name + "_scale"], out=buf, **kw)
         return ops.unshuffle_weight(Ws, out=buf, **kw)
@@ -233,7 +246,7 @@ class LlamaModel:
         B = ids.shape[0]
         sw, SK, ALL = dec["split_ws"], ops.SPLIT_K, ops.SPLIT_K | ops.SPLIT_BALANCE
         for l, lw in enumerate(dec["layers"]):
-            # (``*_scale``: fp8 weights' row scales, absent = bf16)
+            # (``*_scale``: fp8 weights' row scales / mxfp4 weights' block scale bytes, absent = bf16)
             q = ops.skinny_gemm_rope(res, lw["wqkv"], ops.PRO_NORM, positions, self.cos_sin, kv.k_layer(l),
                                      kv.v_layer(l), meta.slot_mapping, self.n_heads, self.n_kv_heads,
                                      self.head_dim, eps, split_ws=sw, split_mode=SK, bias=lw.get("bqkv"),

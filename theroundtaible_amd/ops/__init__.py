@@ -459,6 +459,63 @@ def _fp8_check(x, Ws, wscale, pro, x2, xout, split_ws, who):
         raise ValueError(f"{who}: fp8 weights need K % {FP8_K_RECORD} == 0 (got {x.shape[1]})")
 
 
+MXFP4_K_RECORD = 128     # k elements per mxfp4 weight record (csrc/skinny_core.h): K must be a multiple
+MXFP4_MAX_ROWS = 32      # fused rows on mxfp4 weights: two launches of <= 16
+
+
+def shuffle_weight_mxfp4(W: torch.Tensor, gamma: Optional[torch.Tensor] = None, rope_heads: int = 0,
+                         head_dim: int = 0, swiglu: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """MXFP4 (OCP e2m1 codes + one e8m0 scale byte per 32 consecutive k) weight-only quantisation of
+    a decode linear: ``(Wq uint8 [N, K/2], scale uint8 [N, K/32])``, taken after the RMSNorm
+    ``gamma`` fold (:func:`reference.quantize_mxfp4` is the contract; 17/32 byte per weight). On the
+    GPU the codes are in the MFMA fragment order of csrc/gemm_skinny_fp4.hip and the scale bytes in
+    the order of its lane records; on CPU both stay row-major. Rows as :func:`shuffle_weight_fp8`."""
+    N, K = W.shape
+    if K % MXFP4_K_RECORD or N % 16:
+        raise ValueError(f"mxfp4 weights need K % {MXFP4_K_RECORD} == 0 and N % 16 == 0 (got [{N}, {K}])")
+    if _use_native(W):
+        Wq = torch.empty(N, K // 2, dtype=torch.uint8, device=W.device)
+        scale = torch.empty(N, K // 32, dtype=torch.uint8, device=W.device)
+        native().shuffle_weight_mxfp4(Wq, scale, W.contiguous(), gamma, int(rope_heads), int(head_dim), bool(swiglu))
+        return Wq, scale
+    return ref.quantize_mxfp4(W, gamma, rope_heads, head_dim)
+
+
+def unshuffle_weight_mxfp4(Wq: torch.Tensor, scale: torch.Tensor, rope_heads: int = 0, head_dim: int = 0,
+                           swiglu: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Row-major ``bf16(value(code) * 2^(e-127))`` ``[N, K]`` in natural row order from a
+    :func:`shuffle_weight_mxfp4` pair: the operand of the prefill / unfused GEMMs."""
+    if out is None:
+        out = torch.empty(Wq.shape[0], 2 * Wq.shape[1], dtype=torch.bfloat16, device=Wq.device)
+    if _use_native(Wq):
+        native().unshuffle_weight_mxfp4(out, Wq, scale, int(rope_heads), int(head_dim), bool(swiglu))
+        return out
+    Wd = ref.dequantize_mxfp4(Wq, scale)
+    if rope_heads:
+        inv = torch.empty(Wq.shape[0], dtype=torch.long)
+        inv[ref.rope_row_perm(Wq.shape[0], rope_heads, head_dim)] = torch.arange(Wq.shape[0])
+        Wd = Wd[inv]
+    out.copy_(Wd)
+    return out
+
+
+def _mxfp4_check(x, Ws, wscale, pro, x2, xout, split_ws, who):
+    """The mxfp4 launch has the one-tile forms only, as fp8: refuse everything else loudly."""
+    if Ws.dtype != torch.uint8:
+        raise ValueError(f"{who}: uint8 wscale given but Ws is {Ws.dtype}, not the uint8 codes of shuffle_weight_mxfp4")
+    if pro not in (PRO_PLAIN, PRO_NORM) or x2 is not None or xout is not None:
+        raise ValueError(f"{who}: mxfp4 weights take the PLAIN / NORM prologues only (no x2 / xout)")
+    if split_ws is not None:
+        raise ValueError(f"{who}: mxfp4 weights have no split-K / CU-balanced launch (pass split_ws=None)")
+    if x.shape[0] > MXFP4_MAX_ROWS:
+        raise ValueError(f"{who}: at most {MXFP4_MAX_ROWS} rows on mxfp4 weights (got {x.shape[0]})")
+    if x.shape[1] % MXFP4_K_RECORD:
+        raise ValueError(f"{who}: mxfp4 weights need K % {MXFP4_K_RECORD} == 0 (got {x.shape[1]})")
+    if Ws.dim() != 2 or 2 * Ws.shape[1] != x.shape[1] or wscale.numel() * 16 != Ws.numel():
+        raise ValueError(f"{who}: mxfp4 weights are codes [N, K/2] with scale bytes [N, K/32] "
+                         f"(got {tuple(Ws.shape)} and {tuple(wscale.shape)} for K = {x.shape[1]})")
+
+
 def skinny_gemm(x: torch.Tensor, Ws: torch.Tensor, pro: int = PRO_PLAIN, epi: int = EPI_STORE,
                 res: Optional[torch.Tensor] = None, eps: float = 1e-5, x2: Optional[torch.Tensor] = None,
                 xout: Optional[torch.Tensor] = None, split_ws: Optional[torch.Tensor] = None,
@@ -473,7 +530,20 @@ def skinny_gemm(x: torch.Tensor, Ws: torch.Tensor, pro: int = PRO_PLAIN, epi: in
     tiles run as two K-halves so every CU streams the same bytes.
     ``wscale``: ``Ws`` is the uint8 codes of :func:`shuffle_weight_fp8` and ``wscale`` its scales
     (PLAIN / NORM prologues, no split workspace; 17..32 rows run as two launches of <= 16, rows
-    being independent in every epilogue)."""
+    being independent in every epilogue). A uint8 ``wscale``: ``Ws`` / ``wscale`` are the codes and
+    block scale bytes of :func:`shuffle_weight_mxfp4`, with the same restrictions."""
+    if wscale is not None and wscale.dtype == torch.uint8:
+        _mxfp4_check(x, Ws, wscale, pro, x2, xout, split_ws, "skinny_gemm")
+        if not _use_native(x):
+            return ref.skinny_gemm(x, ref.dequantize_mxfp4(Ws, wscale), pro, epi, res, eps)
+        M = x.shape[0]
+        n = Ws.shape[0] // (2 if epi == EPI_SWIGLU else 1)
+        out = torch.empty(M, n, dtype=x.dtype, device=x.device) if epi != EPI_RESID else x
+        for a in range(0, M, 16):
+            b = min(M, a + 16)
+            native().skinny_gemm_mxfp4(out[a:b], x[a:b], Ws, wscale, pro, epi, res[a:b] if res is not None else None,
+                                       eps)
+        return None if epi == EPI_RESID else out
     if wscale is not None:
         _fp8_check(x, Ws, wscale, pro, x2, xout, split_ws, "skinny_gemm")
         if not _use_native(x):
@@ -487,7 +557,7 @@ def skinny_gemm(x: torch.Tensor, Ws: torch.Tensor, pro: int = PRO_PLAIN, epi: in
                                      eps)
         return None if epi == EPI_RESID else out
     if Ws.dtype == torch.uint8:
-        raise ValueError("skinny_gemm: uint8 (fp8) weights need their wscale")
+        raise ValueError("skinny_gemm: uint8 (fp8 / mxfp4) weights need their wscale")
     if _use_native(x):
         n = Ws.shape[0] // (2 if epi == EPI_SWIGLU else 1)
         out = torch.empty(x.shape[0], n, dtype=x.dtype, device=x.device) if epi != EPI_RESID else x
@@ -509,7 +579,19 @@ def skinny_gemm_rope(x: torch.Tensor, Ws: torch.Tensor, pro: int, positions: tor
     ``bias`` (Qwen2 q/k/v bias, added after the norm scale and before RoPE) must come from
     :func:`rope_bias` (fp32, the shuffled weight's column order).
     ``wscale``: fp8 weights, as in :func:`skinny_gemm` (``Ws`` from ``shuffle_weight_fp8`` with the
-    same ``rope_heads`` / ``head_dim``)."""
+    same ``rope_heads`` / ``head_dim``; uint8 ``wscale``: from ``shuffle_weight_mxfp4``)."""
+    if wscale is not None and wscale.dtype == torch.uint8:
+        _mxfp4_check(x, Ws, wscale, pro, x2, xout, split_ws, "skinny_gemm_rope")
+        if not _use_native(x):
+            return ref.skinny_gemm_rope(x, ref.dequantize_mxfp4(Ws, wscale), pro, positions, cos_sin, k_cache,
+                                        v_cache, slots, n_heads, n_kv_heads, head_dim, eps, None, None, bias)
+        M = x.shape[0]
+        q = torch.empty(M, n_heads, head_dim, dtype=x.dtype, device=x.device)
+        for a in range(0, M, 16):
+            b = min(M, a + 16)
+            native().skinny_gemm_rope_mxfp4(q[a:b], x[a:b], Ws, wscale, pro, positions[a:b], cos_sin, k_cache,
+                                            v_cache, slots[a:b], n_heads, n_kv_heads, head_dim, eps, bias)
+        return q
     if wscale is not None:
         _fp8_check(x, Ws, wscale, pro, x2, xout, split_ws, "skinny_gemm_rope")
         if not _use_native(x):
@@ -523,7 +605,7 @@ def skinny_gemm_rope(x: torch.Tensor, Ws: torch.Tensor, pro: int, positions: tor
                                           slots[a:b], n_heads, n_kv_heads, head_dim, eps, bias)
         return q
     if Ws.dtype == torch.uint8:
-        raise ValueError("skinny_gemm_rope: uint8 (fp8) weights need their wscale")
+        raise ValueError("skinny_gemm_rope: uint8 (fp8 / mxfp4) weights need their wscale")
     if _use_native(x):
         q = torch.empty(x.shape[0], n_heads, head_dim, dtype=x.dtype, device=x.device)
         native().skinny_gemm_rope(q, x, Ws, pro, positions, cos_sin, k_cache, v_cache, slots, n_heads, n_kv_heads,

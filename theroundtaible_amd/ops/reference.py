@@ -257,6 +257,68 @@ def dequantize_fp8(codes, scale):
     return (codes.view(torch.float8_e4m3fn).float() * scale.float()[:, None]).to(torch.bfloat16)
 
 
+MXFP4_BLOCK = 32                                             # k elements per scale byte
+MXFP4_MAGNITUDES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # e2m1, code & 7
+
+
+def mxfp4_scale_byte(amax):
+    """The e8m0 scale byte (int32 tensor) of blocks whose largest ``|wf|`` is the fp32 ``amax``:
+    ``max(E - 2, 2)``, ``E`` the exponent field of ``amax``."""
+    E = (amax.contiguous().view(torch.int32) >> 23) & 0xFF
+    return (E - 2).clamp_min(2)
+
+
+def mxfp4_code(wf, e):
+    """The e2m1 code (uint8 tensor, 0..15) of fp32 ``wf`` under the scale byte(s) ``e`` (int32, 2..252,
+    broadcast against ``wf``): the rule of :func:`quantize_mxfp4`."""
+    wf, e = torch.broadcast_tensors(wf, e)
+    inv = ((254 - e) << 23).to(torch.int32).view(torch.float32)          # 2^(127-e), a normal fp32
+    y = wf.abs() * inv
+    mag = ((y > 0.25).to(torch.uint8) + (y >= 0.75).to(torch.uint8) + (y > 1.25).to(torch.uint8)
+           + (y >= 1.75).to(torch.uint8) + (y > 2.5).to(torch.uint8) + (y >= 3.5).to(torch.uint8)
+           + (y > 5.0).to(torch.uint8))
+    sign = (wf.contiguous().view(torch.int32) < 0).to(torch.uint8)        # the sign BIT: -0.0 counts
+    return mag | (sign << 3)
+
+
+def quantize_mxfp4(W, gamma=None, rope_heads: int = 0, head_dim: int = 0):
+    """The MXFP4 weight-only contract (csrc/fp4_core.h, csrc/gemm_skinny_fp4.hip): row-major OCP
+    e2m1 codes, two per byte (uint8 ``[N, K/2]``: k = 2j in the low nibble of byte j, 2j + 1 in the
+    high), and one e8m0 scale byte per block of 32 consecutive k of a row (uint8 ``[N, K/32]``), of
+    ``wf = fp32(W) * fp32(gamma)`` (no bf16 rounding of the fold). Per block: ``E`` = the fp32
+    exponent field of the largest ``|wf|``, ``e = max(E - 2, 2)`` (the OCP rule floor(log2 amax) -
+    emax(e2m1), floored so 0.5 * 2^(e-127) is a normal bf16; an all-zero block gets e = 2 and zero
+    codes), ``y = |wf| / 2^(e-127)`` (exact), code & 7 = the magnitude of {0, .5, 1, 1.5, 2, 3, 4, 6}
+    nearest to min(y, 6) with ties to the even code, code bit 3 = the sign bit of ``wf``, always.
+    Rows (and their scale bytes) permuted for the ROPE epilogue as :func:`fold_gamma`."""
+    N, K = W.shape
+    if K % MXFP4_BLOCK:
+        raise ValueError(f"mxfp4 blocks are {MXFP4_BLOCK} consecutive k: K = {K} does not divide")
+    wf = W.float() if gamma is None else W.float() * gamma.float()[None, :]
+    blocks = wf.reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    e = mxfp4_scale_byte(blocks.abs().amax(dim=2))
+    c = mxfp4_code(blocks, e[:, :, None]).reshape(N, K // 2, 2)
+    codes = (c[:, :, 0] | (c[:, :, 1] << 4)).contiguous()
+    scale = e.to(torch.uint8)
+    if rope_heads:
+        perm = rope_row_perm(N, rope_heads, head_dim).to(W.device)
+        codes, scale = codes[perm].contiguous(), scale[perm].contiguous()
+    return codes, scale
+
+
+def dequantize_mxfp4(codes, scale):
+    """``bf16(value(code) * 2^(e-127))`` (exact) of row-major :func:`quantize_mxfp4` codes and scale
+    bytes, rows as stored: the weight every mxfp4 GEMM path (fused decode, unfused, prefill)
+    computes with. Any codes and scale bytes in 2..252 are valid, not only the quantiser's."""
+    N, K2 = codes.shape
+    c = torch.stack([codes & 15, codes >> 4], dim=2).reshape(N, 2 * K2).long()
+    table = torch.tensor(MXFP4_MAGNITUDES + tuple(-m for m in MXFP4_MAGNITUDES), dtype=torch.float32,
+                         device=codes.device)
+    two_e = (scale.to(torch.int32) << 23).view(torch.float32)            # 2^(e-127)
+    v = table[c].reshape(N, -1, MXFP4_BLOCK) * two_e.reshape(N, -1)[:, :, None]
+    return v.reshape(N, 2 * K2).to(torch.bfloat16)
+
+
 def skinny_gemm(x, Wf, pro=0, epi=0, res=None, eps=1e-5, x2=None, xout=None):
     """Semantics of csrc/gemm_skinny.hip on the (gamma-folded, row-major) weight ``Wf``:
     y = rsqrt(mean(x^2) + eps)[:, None] * (x @ Wf^T) for the NORM prologue; NORM_ADD (pro=2)
