@@ -29,6 +29,14 @@ __global__ void __launch_bounds__(W * 64) paged_decode_kernel(AttnArgs p) {
   attn_item<D, false, GM, W, PP, LM>(p, blockIdx.x, blockIdx.y, sm_.m);
 }
 
+// The same over an fp8 (e4m3fn) K/V cache: attn_core.h Tile8 (half the tile registers, converted
+// to bf16 fragments in `step`), k_scale inside scale_log2, v_scale where O is normalised.
+template <int D, int GM, bool PP, int LM>
+__global__ void __launch_bounds__(NW * 64) paged_decode_fp8_kernel(AttnArgs p) {
+  __shared__ AttnSmem<D, GM, NW> sm_;
+  attn_item<D, false, GM, NW, PP, LM, true>(p, blockIdx.x, blockIdx.y, sm_);
+}
+
 // Per-step work plan: one workgroup per item (sequence b, split) writes the item's key range
 // (item_range, exactly as attn_item derives it) and its block ids. A decode step runs this once;
 // every layer's attention launch then requests an item header and its first block ids together
@@ -63,7 +71,8 @@ __global__ void __launch_bounds__(256) attn_plan_kernel(AttnArgs p, int G, int G
 // Merge order is fixed (lane-local slots in index order, then xor-shuffle pairs, then a tree
 // over the waves through LDS), so the result does not depend on timing.
 // Partials were stored write-through by the previous launch: the kernel boundary orders them.
-template <int D, int SPL>
+// KV8: the partials came from an fp8 cache, the final rows take the V scale (AttnArgs::v_scale).
+template <int D, int SPL, bool KV8 = false>
 __global__ void __launch_bounds__(1024) decode_combine_kernel(AttnArgs p) {
   const int G = p.Hq / p.Hkv;
   const int row = blockIdx.x;                  // b * Hq + query head
@@ -152,7 +161,8 @@ __global__ void __launch_bounds__(1024) decode_combine_kernel(AttnArgs p) {
 #pragma unroll
     for (int x = 8; x < 64; x <<= 1) xmerge(x, w & (x >> 3));
     if (w == 0) {
-      const float inv = L > 0.f ? 1.f / L : 0.f;
+      float inv = L > 0.f ? 1.f / L : 0.f;
+      if constexpr (KV8) inv *= p.v_scale;
       store_bf16x4(p.out + (size_t)row * D + d0, O[0] * inv, O[1] * inv, O[2] * inv, O[3] * inv, false);
     }
   }
@@ -184,14 +194,15 @@ int attn_group_cols() { return GROUP_COLS; }
 // (zeroed once). groups: nullptr or [B][3] {first, n, shared blocks} (shared-prefix groups,
 // attn_core.h); slot_stride >= max n * num_splits (0 = num_splits, no groups).
 // Returns 0, the plan's refusal (attn_plan.h AttnPlan::rc: -1 .. -5) or -6: a launch failed.
-int launch_paged_decode(void* out, const void* q, const void* k_cache, const void* v_cache, const int* block_tables,
-                        const int* ctx_lens, float* part_o, float* part_ml, int* counters, int B, int Hq, int Hkv,
-                        int D, int max_blocks, float scale, int num_splits, const int* groups, int slot_stride,
-                        hipStream_t stream, int defer_combine, int* deferred, const int* plan, int plan_stride) {
+static int decode_launch(void* out, const void* q, const void* k_cache, const void* v_cache, const int* block_tables,
+                         const int* ctx_lens, float* part_o, float* part_ml, int* counters, int B, int Hq, int Hkv,
+                         int D, int max_blocks, float scale, int num_splits, const int* groups, int slot_stride,
+                         hipStream_t stream, int defer_combine, int* deferred, const int* plan, int plan_stride,
+                         bool kv_fp8, float k_scale, float v_scale) {
   if (deferred != nullptr) *deferred = 0;
   const AttnKnobs& kn = knobs();
   const AttnPlan pl = plan_paged_decode(B, Hq, Hkv, D, num_splits, groups != nullptr, slot_stride, plan != nullptr,
-                                        plan_stride, defer_combine != 0, kn);
+                                        plan_stride, defer_combine != 0, kn, kv_fp8);
   if (pl.rc != 0 || pl.gx == 0) return pl.rc;
   AttnArgs args{(uint16_t*)out, (const uint16_t*)q, (const uint16_t*)k_cache, (const uint16_t*)v_cache,
                 block_tables, ctx_lens, part_o, part_ml, counters, Hq, Hkv, max_blocks, scale * LOG2E, pl.splits,
@@ -200,6 +211,23 @@ int launch_paged_decode(void* out, const void* q, const void* k_cache, const voi
   args.ext_combine = pl.ext_combine ? 1 : 0;
   args.plan = plan;
   args.plan_stride = plan != nullptr ? plan_stride : 0;
+  if (kv_fp8) {
+    // value = e4m3(code) * scale: k_scale joins the softmax scale, v_scale the final normalisation
+    args.scale_log2 = scale * k_scale * LOG2E;
+    args.v_scale = v_scale;
+    int rc8 = with_const<4, 8, 16>(pl.GM, [&](auto gm) {
+      return with_const<1, 0>(pl.pp, [&](auto pp) {
+        return with_const<0, 1, 2, 3>(pl.lm, [&](auto lm) {
+          return launch(paged_decode_fp8_kernel<128, gm(), pp() != 0, lm()>, dim3(pl.gx, pl.gy), dim3(pl.block),
+                        stream, args);
+        });
+      });
+    });
+    if (rc8 != 0 || !pl.combine) return rc8;
+    return with_const<1, 2, 4, 8>(pl.spl, [&](auto spl) {
+      return launch(decode_combine_kernel<128, spl(), true>, dim3(pl.cgx, pl.cgy), dim3(pl.cblock), stream, args);
+    });
+  }
   int rc = with_const<128, 64>(D, [&](auto d) {
     return with_const<4, 8, 16>(pl.GM, [&](auto gm) {
       return with_const<1, 0>(pl.pp, [&](auto pp) {
@@ -218,6 +246,29 @@ int launch_paged_decode(void* out, const void* q, const void* k_cache, const voi
       return launch(decode_combine_kernel<d(), spl()>, dim3(pl.cgx, pl.cgy), dim3(pl.cblock), stream, args);
     });
   });
+}
+
+int launch_paged_decode(void* out, const void* q, const void* k_cache, const void* v_cache, const int* block_tables,
+                        const int* ctx_lens, float* part_o, float* part_ml, int* counters, int B, int Hq, int Hkv,
+                        int D, int max_blocks, float scale, int num_splits, const int* groups, int slot_stride,
+                        hipStream_t stream, int defer_combine, int* deferred, const int* plan, int plan_stride) {
+  return decode_launch(out, q, k_cache, v_cache, block_tables, ctx_lens, part_o, part_ml, counters, B, Hq, Hkv, D,
+                       max_blocks, scale, num_splits, groups, slot_stride, stream, defer_combine, deferred, plan,
+                       plan_stride, false, 1.f, 1.f);
+}
+
+// The same over an fp8 K/V cache (e4m3fn bytes in the layouts of common.h kc8_elem / vc8_elem, same
+// tensor shapes; k_scale / v_scale: value = e4m3(code) * scale). D = 128 only (-7 otherwise); a
+// scale that is not finite and > 0 is -8, before any HIP call. The combine is never deferred.
+int launch_paged_decode_fp8(void* out, const void* q, const void* k_cache, const void* v_cache,
+                            const int* block_tables, const int* ctx_lens, float* part_o, float* part_ml,
+                            int* counters, int B, int Hq, int Hkv, int D, int max_blocks, float scale, int num_splits,
+                            const int* groups, int slot_stride, hipStream_t stream, const int* plan, int plan_stride,
+                            float k_scale, float v_scale) {
+  if (!(k_scale > 0.f) || !(v_scale > 0.f) || !(k_scale <= 3.0e38f) || !(v_scale <= 3.0e38f)) return -8;
+  return decode_launch(out, q, k_cache, v_cache, block_tables, ctx_lens, part_o, part_ml, counters, B, Hq, Hkv, D,
+                       max_blocks, scale, num_splits, groups, slot_stride, stream, 0, nullptr, plan, plan_stride, true,
+                       k_scale, v_scale);
 }
 
 // The per-step plan for launch_paged_decode's ``plan`` (same B, heads, num_splits, groups, block

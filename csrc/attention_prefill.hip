@@ -302,3 +302,19 @@ int launch_prefill_split(void* out, const void* q, const void* k_cache, const vo
 }
 
 int prefill_split_supported(int G, int D) { return use_prefill32(G, D) ? 1 : 0; }
+
+// fp8 K/V caches (kv_dtype "fp8"): the 32x32 kernel only — a shape that would take this file's
+// 16x16 kernel (D != 128, G > 8, or ROUNDTABLE_PREFILL16) is refused with -1, not run on bf16 math
+// over fp8 bytes. map_stride 2: tile_map is whole tiles; 5: key-split items + cmap.
+int launch_prefill32_fp8(void* out, const void* q, const void* k_cache, const void* v_cache, const int* block_tables,
+                         const int* cu_q, const int* start_pos, const int* tile_map, int n_tiles, int Hq, int Hkv,
+                         int max_blocks, float scale, hipStream_t stream, int map_stride, const int* cmap, int n_split,
+                         float* part_o, float* part_ml, float k_scale, float v_scale);
+int launch_prefill_fp8(void* out, const void* q, const void* k_cache, const void* v_cache, const int* block_tables,
+                       const int* cu_q, const int* start_pos, const int* tile_map, int n_tiles, int map_stride,
+                       const int* cmap, int n_split, float* part_o, float* part_ml, int Hq, int Hkv, int D,
+                       int max_blocks, float scale, float k_scale, float v_scale, hipStream_t stream) {
+  if (Hkv < 1 || Hq < 1 || Hq % Hkv || !use_prefill32(Hq / Hkv, D)) return -1;
+  return launch_prefill32_fp8(out, q, k_cache, v_cache, block_tables, cu_q, start_pos, tile_map, n_tiles, Hq, Hkv,
+                              max_blocks, scale, stream, map_stride, cmap, n_split, part_o, part_ml, k_scale, v_scale);
+}

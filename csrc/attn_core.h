@@ -107,6 +107,44 @@ RT_DEVICE void load_tile(Tile<D>& t, const uint16_t* __restrict__ kblk, const ui
   }
 }
 
+// ---- FP8 K/V tiles (kv_dtype "fp8": e4m3fn codes, kv_fp8_core.h; block layouts common.h kc8_elem /
+// vc8_elem). Half the registers per tile, the same number of tiles in flight. A lane's 16 B of K
+// is dims 64c + 16g .. +15 of key krow + 4h: two A fragments, fed against Q fragments 2c and 2c + 1,
+// which hold d = 64c + 16g + 8u + j (the same permutation of d on K and Q). A lane's 16 B of V is
+// keys 8g..8g+7 of dims 32e + r and 32e + 16 + r: the B fragments of output chunks 2e and 2e + 1.
+template <int D>
+struct Tile8 {
+  short8 k[2][D / 64];
+  short8 v[D / 32];
+};
+
+template <int D, int LM = 0>
+RT_DEVICE void load_tile(Tile8<D>& t, const uint8_t* __restrict__ kblk, const uint8_t* __restrict__ vblk, int r,
+                         int g) {
+  const int krow = 8 * (r >> 2) + (r & 3);
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int c = 0; c < D / 64; ++c)
+      t.k[h][c] = ld16<(LM & LM_NTK) != 0>(reinterpret_cast<const uint16_t*>(kblk + rt::kc8_elem(BS, krow + 4 * h, 64 * c + 16 * g)));
+#pragma unroll
+  for (int e = 0; e < D / 32; ++e)
+    t.v[e] = ld16<(LM & LM_NTV) != 0>(reinterpret_cast<const uint16_t*>(vblk + rt::vc8_elem(BS, 8 * g, 32 * e + r)));
+}
+
+using rt::kv8_frag;   // 8 code bytes -> one bf16 fragment (common.h)
+
+template <int D, bool KV8>
+struct TileOf {
+  typedef Tile<D> type;
+  typedef uint16_t elem;
+};
+template <int D>
+struct TileOf<D, true> {
+  typedef Tile8<D> type;
+  typedef uint8_t elem;
+};
+
 struct AttnArgs {
   uint16_t* out;               // [B, Hq, D]
   const uint16_t* q;           // [B, Hq, D]
@@ -130,6 +168,9 @@ struct AttnArgs {
   // (sequence, split), PLAN_HDR header ints then the item's block ids, plan_stride ints per item
   const int* plan = nullptr;
   int plan_stride = 0;
+  // fp8 caches (KV8 instantiations only): the V scale, one fp32 multiply where O is normalised
+  // (k_scale is already inside scale_log2)
+  float v_scale = 1.f;
 };
 
 // The key range of work item (sequence b, split) — shared chunk of its group's prefix, then its
@@ -214,12 +255,16 @@ RT_DEVICE void store_bf16x4(uint16_t* dst, float a, float b_, float c, float d, 
 // W = waves per workgroup (8: 16 were measured and rejected, attn_plan.h).
 // PP: ping-pong K/V tiles (two in flight per wave); false = the round-4 cur/nxt copy loop (A/B)
 // LM: K/V load mode (LM_NTK / LM_NTV above)
-template <int D, bool SC1, int GM = 16, int W = NW, bool PP = true, int LM = 0>
+// KV8: the caches hold e4m3fn bytes (Tile8); D = 128, no SC1, no LM_GLDS
+template <int D, bool SC1, int GM = 16, int W = NW, bool PP = true, int LM = 0, bool KV8 = false>
 RT_DEVICE bool attn_item(const AttnArgs& P, int bh, int split, AttnSmem<D, GM, W>& S) {
+  static_assert(!KV8 || (D % 64 == 0 && !SC1 && (LM & LM_GLDS) == 0), "fp8 K/V: plain loads, D % 64 == 0");
+  typedef typename TileOf<D, KV8>::type TileT;
+  typedef typename TileOf<D, KV8>::elem CacheT;
   uint16_t* __restrict__ out = P.out;
   const uint16_t* __restrict__ q = P.q;
-  const uint16_t* __restrict__ k_cache = P.k_cache;
-  const uint16_t* __restrict__ v_cache = P.v_cache;
+  const CacheT* __restrict__ k_cache = reinterpret_cast<const CacheT*>(P.k_cache);
+  const CacheT* __restrict__ v_cache = reinterpret_cast<const CacheT*>(P.v_cache);
   const int* __restrict__ block_tables = P.block_tables;
   const int* __restrict__ ctx_lens = P.ctx_lens;
   float* __restrict__ part_o = P.part_o;
@@ -239,7 +284,8 @@ RT_DEVICE bool attn_item(const AttnArgs& P, int bh, int split, AttnSmem<D, GM, W
   const int rseq = r / G, rhead = r - (r / G) * G;  // column r -> (member, head within the kv group)
   // reduction-dim order of the QK^T MFMAs: lane group g holds d = 32c + 8g.. of chunk c (the same
   // permutation of d for Q and K; it matches the chunk-major K block)
-  const int kg = 8 * g, kc = 32;
+  // (fp8 K: fragment 2c + u holds d = 64c + 16g + 8u.., Tile8)
+  const int kg = KV8 ? 16 * g : 8 * g, kc = 32;
   const bool grouped = P.groups != nullptr;
   ItemRange ir;
   // planned: the item's header and this wave's first 64 block ids are requested together, both
@@ -284,7 +330,7 @@ RT_DEVICE bool attn_item(const AttnArgs& P, int bh, int split, AttnSmem<D, GM, W
       if constexpr (SC1)   // uniform base + per-lane offset (a per-lane resource would waterfall)
         v = __builtin_bit_cast(short8, rt::sc1_load4(rt::buf_rsrc(q), (int)((qr - q) + kc * c) * 2));
       else
-        v = *reinterpret_cast<const short8*>(qr + kc * c);
+        v = *reinterpret_cast<const short8*>(qr + (KV8 ? 64 * (c >> 1) + 8 * (c & 1) : kc * c));
       if (!live) v = short8{0, 0, 0, 0, 0, 0, 0, 0};
       qf[c] = v;
     }
@@ -311,25 +357,33 @@ RT_DEVICE bool attn_item(const AttnArgs& P, int bh, int split, AttnSmem<D, GM, W
     return tt < nv ? (plan_ids != nullptr && tt < maxt ? plan_ids[tt] : bt_entry(tt)) : 0;
   };
   // tile vn = wid + W*j into t (j: the wave's tile index, uniform)
-  auto fetch = [&](Tile<D>& t, int vn, int j) {
+  auto fetch = [&](TileT& t, int vn, int j) {
     if ((j & 63) == 0 && !(j == 0 && plan_ids != nullptr && W * 64 <= maxt)) {
       const int tt = vn + W * lane;
       blk_lane = blk_of(tt);
     }
     const size_t base = (size_t)__builtin_amdgcn_readlane(blk_lane, j & 63) * blk_stride + (size_t)hk * BS * D;
-    load_tile<D, SC1, LM>(t, k_cache + base, v_cache + base, r, g);
+    if constexpr (KV8)
+      load_tile<D, LM>(t, k_cache + base, v_cache + base, r, g);
+    else
+      load_tile<D, SC1, LM>(t, k_cache + base, v_cache + base, r, g);
   };
   // one 32-key tile: S^T = K Q^T, online softmax down each column, O += P V
-  auto step = [&](const Tile<D>& cur, int v) {
+  auto step = [&](const TileT& cur, int v) {
     // ---- S^T = K Q^T ----
     float4_ s[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       s[h] = float4_{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int c = 0; c < D / 32; ++c)
-        s[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, cur.k[h][c]),
-                                                       __builtin_bit_cast(bf16x8, qf[c]), s[h], 0, 0, 0);
+      for (int c = 0; c < D / 32; ++c) {
+        bf16x8 ka;
+        if constexpr (KV8)
+          ka = kv8_frag(cur.k[h][c >> 1], c & 1);
+        else
+          ka = __builtin_bit_cast(bf16x8, cur.k[h][c]);
+        s[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka, __builtin_bit_cast(bf16x8, qf[c]), s[h], 0, 0, 0);
+      }
     }
     // ---- online softmax down column r: lane holds keys 8g + 4h + i. Shared tiles are live
     // for every member's columns (full blocks); private tiles only for b's own, below ctx. ----
@@ -375,8 +429,12 @@ RT_DEVICE bool attn_item(const AttnArgs& P, int bh, int split, AttnSmem<D, GM, W
       float4_ o = oacc[e];
 #pragma unroll
       for (int i = 0; i < 4; ++i) o[i] *= al[i];
-      oacc[e] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, pa),
-                                                        __builtin_bit_cast(bf16x8, cur.v[e]), o, 0, 0, 0);
+      bf16x8 vb;
+      if constexpr (KV8)
+        vb = kv8_frag(cur.v[e >> 1], e & 1);
+      else
+        vb = __builtin_bit_cast(bf16x8, cur.v[e]);
+      oacc[e] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, pa), vb, o, 0, 0, 0);
     }
   };
   if constexpr ((LM & LM_GLDS) != 0 && !SC1) {
@@ -437,7 +495,7 @@ RT_DEVICE bool attn_item(const AttnArgs& P, int bh, int split, AttnSmem<D, GM, W
     // j+1's 16 loads are always issued before tile j's math, which then waits with vmcnt(16):
     // two tiles (32 KB) in flight per wave. Past the end the prefetch re-reads the tile being
     // computed (an L2 hit, once per wave).
-    auto prefetch = [&](Tile<D>& t, int vn, int j) {
+    auto prefetch = [&](TileT& t, int vn, int j) {
       const bool past = vn >= nv;
       const int jj = past ? j - 1 : j;
       if (!past && (j & 63) == 0) {
@@ -445,9 +503,12 @@ RT_DEVICE bool attn_item(const AttnArgs& P, int bh, int split, AttnSmem<D, GM, W
         blk_lane = blk_of(tt);
       }
       const size_t base = (size_t)__builtin_amdgcn_readlane(blk_lane, jj & 63) * blk_stride + (size_t)hk * BS * D;
-      load_tile<D, SC1, LM>(t, k_cache + base, v_cache + base, r, g);
+      if constexpr (KV8)
+        load_tile<D, LM>(t, k_cache + base, v_cache + base, r, g);
+      else
+        load_tile<D, SC1, LM>(t, k_cache + base, v_cache + base, r, g);
     };
-    Tile<D> ta, tb;
+    TileT ta, tb;
     if (v < nv) {
       fetch(ta, v, 0);
       int j = 1;
@@ -465,7 +526,7 @@ RT_DEVICE bool attn_item(const AttnArgs& P, int bh, int split, AttnSmem<D, GM, W
       }
     }
   } else {
-    Tile<D> cur, nxt;
+    TileT cur, nxt;
     if (v < nv) fetch(cur, v, 0);
     for (int j = 1; v < nv; v += W, ++j) {
       const int vn = v + W;
@@ -517,7 +578,8 @@ RT_DEVICE bool attn_item(const AttnArgs& P, int bh, int split, AttnSmem<D, GM, W
       }
     }
     if (nslots == 1) {
-      const float inv = L > 0.f ? 1.f / L : 0.f;
+      float inv = L > 0.f ? 1.f / L : 0.f;
+      if constexpr (KV8) inv *= P.v_scale;
       store_bf16x4(out + (q0 + row) * D + d0, O[0] * inv, O[1] * inv, O[2] * inv, O[3] * inv, SC1);
     } else {   // partials leave as 16-B write-through (sc1) stores: the combining workgroup, possibly
       // on another XCD, reads them with sc1 loads and no L2 writeback/invalidate is needed
@@ -639,7 +701,8 @@ RT_DEVICE bool attn_item(const AttnArgs& P, int bh, int split, AttnSmem<D, GM, W
     }
   }
   if (grp == 0) {
-    const float inv = Lr > 0.f ? 1.f / Lr : 0.f;
+    float inv = Lr > 0.f ? 1.f / Lr : 0.f;
+    if constexpr (KV8) inv *= P.v_scale;
     store_bf16x4(out + (q0 + row) * D + d0, O[0] * inv, O[1] * inv, O[2] * inv, O[3] * inv, SC1);
   }
   __syncthreads();

@@ -50,7 +50,8 @@ RT_HD int combine_slot_bound(bool grouped, int G, int num_splits, int stride) {
 
 struct AttnPlan {
   int rc = 0;                  // 0, or -1 head ratio, -3 splits > MAXS, -4 group slots < splits,
-                               // -5 plan row without ids, -2 head dim (launch_paged_decode adds -6)
+                               // -5 plan row without ids, -2 head dim (launch_paged_decode adds -6),
+                               // -7 fp8 cache with a head dim other than 128
   int splits = 1;              // num_splits, at least 1
   int gx = 0, gy = 0, block = NW * 64;   // attention launch; gx == 0: empty batch, nothing runs
   int GM = GROUP_COLS;         // query columns the workgroup's LDS holds
@@ -65,7 +66,8 @@ struct AttnPlan {
 };
 
 inline AttnPlan plan_paged_decode(int B, int Hq, int Hkv, int D, int num_splits, bool grouped, int slot_stride,
-                                  bool has_plan, int plan_stride, bool defer_combine, const AttnKnobs& kn) {
+                                  bool has_plan, int plan_stride, bool defer_combine, const AttnKnobs& kn,
+                                  bool kv_fp8 = false) {
   AttnPlan pl;
   if (B == 0) return pl;
   pl.splits = num_splits < 1 ? 1 : num_splits;
@@ -74,6 +76,7 @@ inline AttnPlan plan_paged_decode(int B, int Hq, int Hkv, int D, int num_splits,
           : grouped && slot_stride < pl.splits       ? -4
           : has_plan && plan_stride <= PLAN_HDR      ? -5
           : D != 128 && D != 64                      ? -2
+          : kv_fp8 && D != 128                       ? -7   // fp8 caches: D = 128 only
                                                      : 0;
   if (pl.rc != 0) return pl;
   const int G = Hq / Hkv;
@@ -97,14 +100,16 @@ inline AttnPlan plan_paged_decode(int B, int Hq, int Hkv, int D, int num_splits,
   // over one 22K prefix without groups, 33.5 -> 35.4: the 2nd / 3rd reads no longer hit L2 / MALL)
   // — the engine decodes shared prefixes as groups, so that case does not arise there.
   // RT_ATTN_LM pins the mode (A/B; 7 = both through the LDS-DMA staged loop, ping-pong form only).
-  pl.lm = (kn.lm & LM_GLDS) && pl.pp ? 7 : kn.lm & 3;
+  // An fp8 cache has the register forms only: RT_ATTN_LM=7 falls back to its two nt bits.
+  pl.lm = (kn.lm & LM_GLDS) && pl.pp && !kv_fp8 ? 7 : kn.lm & 3;
   // separate combine launch from this many splits on (RT_ATTN_EXT_SPLITS pins it; 0 = never):
   // r03 probes, 3 knights x 40K shared keys: in-launch combine 8.7 us at 16 splits (48 slots),
   // 23 us at 64 (192 slots); whole launch(es), grouped B=3: tp8 shard 32.6 -> 14.9 us (64
   // splits), tp1 41.0 -> 38.7 us (8 splits) — the extra boundary costs less than the serial
   // combine on one CU at every measured split count (profiles/r03/attn_ext_combine.md)
   pl.ext_combine = kn.ext_splits > 0 && pl.splits >= kn.ext_splits && kn.probe == 0;
-  pl.deferred = pl.ext_combine && defer_combine && D == 128;
+  // (never with an fp8 cache: the caller's combine does not know the V scale)
+  pl.deferred = pl.ext_combine && defer_combine && D == 128 && !kv_fp8;
   pl.combine = pl.ext_combine && !pl.deferred && !kn.skip_combine;
   if (!pl.combine) return pl;
   pl.nmax = combine_slot_bound(grouped, G, pl.splits, slot_stride);

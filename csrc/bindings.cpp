@@ -6,6 +6,7 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <vector>
 
 #include "grammar_plan.h"
@@ -128,7 +129,24 @@ int launch_skinny_gemm_rope_fp4(void* q_out, const void* x, const void* Wq, cons
                                 int pro, float eps, const int64_t* positions, const float* cos_sin, void* k_cache,
                                 void* v_cache, const int64_t* slots, int Hq, int Hkv, int D, int BS,
                                 const float* bias, hipStream_t stream);
-
+// fp8 K/V cache (kv_dtype "fp8"): rope_cache.hip, attention_decode.hip, attention_prefill.hip, gemm_skinny.hip
+int launch_rope_cache_fp8(void* q_out, const void* qkv, const int64_t* positions, const float* cos_sin,
+                          void* k_cache, void* v_cache, const int64_t* slots, int T, int Hq, int Hkv, int D, int BS,
+                          int64_t qkv_stride, bool rope, float k_scale, float v_scale, hipStream_t stream);
+int launch_paged_decode_fp8(void* out, const void* q, const void* k_cache, const void* v_cache,
+                            const int* block_tables, const int* ctx_lens, float* part_o, float* part_ml,
+                            int* counters, int B, int Hq, int Hkv, int D, int max_blocks, float scale, int num_splits,
+                            const int* groups, int slot_stride, hipStream_t stream, const int* plan, int plan_stride,
+                            float k_scale, float v_scale);
+int launch_prefill_fp8(void* out, const void* q, const void* k_cache, const void* v_cache, const int* block_tables,
+                       const int* cu_q, const int* start_pos, const int* tile_map, int n_tiles, int map_stride,
+                       const int* cmap, int n_split, float* part_o, float* part_ml, int Hq, int Hkv, int D,
+                       int max_blocks, float scale, float k_scale, float v_scale, hipStream_t stream);
+int launch_skinny_gemm_rope_kv8(int wt, void* q_out, const void* x, const void* W, const void* wscale, int M, int K,
+                                int pro, float eps, const int64_t* positions, const float* cos_sin, void* k_cache,
+                                void* v_cache, const int64_t* slots, int Hq, int Hkv, int D, int BS, const void* x2,
+                                void* xo, hipStream_t stream, int* split_ws, int64_t split_ws_ints, int split_mode,
+                                const float* bias, float k_scale, float v_scale);
 
 namespace {
 hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
@@ -182,9 +200,17 @@ void fused_add_layer_norm(torch::Tensor out, torch::Tensor x, torch::Tensor res,
   norm_common(out, x, &res, w, &b, eps, true);
 }
 
-void check_caches(const torch::Tensor& kc, const torch::Tensor& vc, int64_t Hkv, int64_t D) {
-  check_bf16(kc, "k_cache");
-  check_bf16(vc, "v_cache");
+// fp8 = false: bf16 caches; true: the one-byte caches of kv_dtype "fp8" (uint8 e4m3fn codes)
+void check_caches(const torch::Tensor& kc, const torch::Tensor& vc, int64_t Hkv, int64_t D, bool fp8 = false) {
+  TORCH_CHECK(kc.scalar_type() == vc.scalar_type(), "k_cache and v_cache must have one dtype (mixed K/V cache dtypes: ",
+              kc.scalar_type(), " / ", vc.scalar_type(), ")");
+  if (fp8) {
+    check_type(kc, torch::kUInt8, "k_cache (fp8 KV: uint8 e4m3fn codes)");
+    check_type(vc, torch::kUInt8, "v_cache (fp8 KV: uint8 e4m3fn codes)");
+  } else {
+    check_bf16(kc, "k_cache");
+    check_bf16(vc, "v_cache");
+  }
   TORCH_CHECK(kc.dim() == 4 && vc.dim() == 4, "caches must be 4-D");
   TORCH_CHECK(kc.size(1) == Hkv && kc.size(3) == D, "k_cache must be [NB, Hkv, BS, D]");
   TORCH_CHECK(vc.size(0) == kc.size(0) && vc.size(1) == Hkv && vc.size(2) == D && vc.size(3) == kc.size(2),
@@ -474,14 +500,14 @@ std::pair<int*, int64_t> split_workspace(const c10::optional<torch::Tensor>& spl
 const float* rope_operands(const char* who, const torch::Tensor& q_out, const torch::Tensor& x, int64_t M,
                            const torch::Tensor& positions, const torch::Tensor& cos_sin, const torch::Tensor& k_cache,
                            const torch::Tensor& v_cache, const torch::Tensor& slots, int64_t Hq, int64_t Hkv, int64_t D,
-                           const c10::optional<torch::Tensor>& bias) {
+                           const c10::optional<torch::Tensor>& bias, bool kv_fp8 = false) {
   TORCH_CHECK(q_out.numel() == M * Hq * D, "q_out must be [M, Hq, D]");
   check_type(positions, torch::kInt64, "positions");
   check_type(slots, torch::kInt64, "slots");
   check_type(cos_sin, torch::kFloat32, "cos_sin");
   TORCH_CHECK(positions.numel() >= M && slots.numel() >= M, "positions/slots must cover M rows");
   TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == D, "cos_sin must be [max_pos, D]");
-  check_caches(k_cache, v_cache, Hkv, D);
+  check_caches(k_cache, v_cache, Hkv, D, kv_fp8);
   if (!bias.has_value()) return nullptr;
   TORCH_CHECK(bias->scalar_type() == torch::kFloat32 && bias->is_contiguous() &&
                   bias->numel() == (Hq + 2 * Hkv) * D && bias->device() == x.device(),
@@ -915,8 +941,17 @@ void unshuffle_weight(torch::Tensor W, torch::Tensor Ws, int64_t rope_heads, int
   TORCH_CHECK(rc == 0, "unshuffle_weight: unsupported configuration (rc=", rc, ")");
 }
 void kv_block_copy(torch::Tensor k, torch::Tensor v, torch::Tensor src, torch::Tensor dst) {
-  check_bf16(k, "k_cache");
-  check_bf16(v, "v_cache");
+  // bf16 pools, or the uint8 pools of kv_dtype "fp8": the kernel moves bytes, in 2-byte units
+  TORCH_CHECK(k.scalar_type() == v.scalar_type(), "kv_block_copy: mixed K/V cache dtypes");
+  const bool fp8 = k.scalar_type() == torch::kUInt8;
+  if (fp8) {
+    check_type(k, torch::kUInt8, "k_cache");
+    check_type(v, torch::kUInt8, "v_cache");
+    TORCH_CHECK(k.dim() == 3 && k.size(2) % 16 == 0, "kv_block_copy: fp8 block bytes must be a multiple of 16");
+  } else {
+    check_bf16(k, "k_cache");
+    check_bf16(v, "v_cache");
+  }
   TORCH_CHECK(k.dim() == 3 && k.sizes() == v.sizes(), "caches must be [L, NB, block_elems]");
   check_type(src, torch::kInt32, "src");
   check_type(dst, torch::kInt32, "dst");
@@ -933,7 +968,8 @@ void kv_block_copy(torch::Tensor k, torch::Tensor v, torch::Tensor src, torch::T
     seen[b] = 1;
   }
   const int rc = launch_kv_block_copy(k.data_ptr(), v.data_ptr(), src.data_ptr<int>(), dst.data_ptr<int>(),
-                                      (int)src.numel(), (int)k.size(0), (int)nb, k.size(2), cur_stream());
+                                      (int)src.numel(), (int)k.size(0), (int)nb, fp8 ? k.size(2) / 2 : k.size(2),
+                                      cur_stream());
   TORCH_CHECK(rc == 0, "kv_block_copy: unsupported configuration (rc=", rc, ")");
 }
 
@@ -1083,9 +1119,214 @@ void skinny_gemm_rope_mxfp4(torch::Tensor q_out, torch::Tensor x, torch::Tensor 
                                              (int)k_cache.size(2), bp, cur_stream());
   TORCH_CHECK(rc == 0, "skinny_gemm_rope_mxfp4: unsupported configuration (rc=", rc, ")");
 }
+
+// ---- FP8 K/V cache (kv_dtype "fp8"): uint8 e4m3fn codes in tensors of the bf16 caches' shapes,
+// value = e4m3(code) * scale (csrc/kv_fp8_core.h; block byte order: common.h kc8_elem / vc8_elem).
+// Every entry point refuses bf16 or mixed caches, head dims the fp8 kernels lack, and scales that
+// are not finite and > 0.
+void check_kv_scales(double k_scale, double v_scale, const char* who) {
+  TORCH_CHECK(std::isfinite(k_scale) && std::isfinite(v_scale) && k_scale > 0 && v_scale > 0 &&
+                  (float)k_scale > 0.f && (float)v_scale > 0.f && std::isfinite((float)k_scale) &&
+                  std::isfinite((float)v_scale),
+              who, ": k_scale / v_scale must be finite and > 0 (got ", k_scale, ", ", v_scale, ")");
+}
+
+void rope_and_cache_fp8(torch::Tensor q_out, torch::Tensor qkv, torch::Tensor positions, torch::Tensor cos_sin,
+                        torch::Tensor k_cache, torch::Tensor v_cache, torch::Tensor slots, int64_t Hq, int64_t Hkv,
+                        int64_t D, double k_scale, double v_scale) {
+  check_bf16(q_out, "q_out");
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == torch::kBFloat16 && qkv.stride(-1) == 1, "qkv must be bf16 rows");
+  check_type(positions, torch::kInt64, "positions");
+  check_type(slots, torch::kInt64, "slot_mapping");
+  check_caches(k_cache, v_cache, Hkv, D, true);
+  check_kv_scales(k_scale, v_scale, "rope_and_cache (fp8 KV)");
+  const int64_t T = qkv.size(0);
+  TORCH_CHECK(qkv.size(1) == (Hq + 2 * Hkv) * D, "qkv width mismatch");
+  TORCH_CHECK(positions.numel() == T && slots.numel() == T && q_out.numel() == T * Hq * D, "token count mismatch");
+  TORCH_CHECK(D > 0 && D % 64 == 0 && k_cache.size(2) % 8 == 0,
+              "fp8 KV: head_dim must be a multiple of 64 and block_size of 8 (block layouts [D/64][BS][64], "
+              "[D/32][16][BS/8][2][8])");
+  const bool rope = cos_sin.numel() > 0;
+  if (rope) {
+    check_type(cos_sin, torch::kFloat32, "cos_sin");
+    TORCH_CHECK(cos_sin.size(1) == D, "cos_sin must be [max_pos, D]");
+  }
+  const int rc = launch_rope_cache_fp8(q_out.data_ptr(), qkv.data_ptr(), positions.data_ptr<int64_t>(),
+                                       rope ? cos_sin.data_ptr<float>() : nullptr, k_cache.data_ptr(),
+                                       v_cache.data_ptr(), slots.data_ptr<int64_t>(), (int)T, (int)Hq, (int)Hkv, (int)D,
+                                       (int)k_cache.size(2), qkv.stride(0), rope, (float)k_scale, (float)v_scale,
+                                       cur_stream());
+  TORCH_CHECK(rc == 0, "rope_and_cache (fp8 KV): unsupported configuration (rc=", rc, ")");
+}
+
+void paged_attention_decode_fp8(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
+                                torch::Tensor block_tables, torch::Tensor ctx_lens, double scale, int64_t num_splits,
+                                torch::Tensor part_o, torch::Tensor part_ml, torch::Tensor counters,
+                                c10::optional<torch::Tensor> groups, int64_t slot_stride,
+                                c10::optional<torch::Tensor> plan, int64_t plan_stride, double k_scale,
+                                double v_scale) {
+  check_bf16(out, "out");
+  check_bf16(q, "q");
+  TORCH_CHECK(q.dim() == 3, "q must be [B, Hq, D]");
+  const int64_t B = q.size(0), Hq = q.size(1), D = q.size(2);
+  TORCH_CHECK(k_cache.dim() == 4, "caches must be 4-D");
+  check_caches(k_cache, v_cache, k_cache.size(1), D, true);
+  check_kv_scales(k_scale, v_scale, "paged_attention_decode (fp8 KV)");
+  TORCH_CHECK(D == 128, "paged_attention_decode: kv_dtype fp8 needs head_dim 128 (got ", D, ")");
+  TORCH_CHECK(k_cache.size(2) == 32, "decode kernel requires kv block_size == 32");
+  check_type(block_tables, torch::kInt32, "block_tables");
+  check_type(ctx_lens, torch::kInt32, "ctx_lens");
+  TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) >= B && ctx_lens.numel() >= B, "metadata shape");
+  const int* gp = nullptr;
+  int64_t stride = num_splits;
+  if (groups.has_value() && groups->defined()) {
+    check_type(*groups, torch::kInt32, "groups");
+    TORCH_CHECK(groups->numel() >= 3 * B, "groups must be [B, 3] int32");
+    TORCH_CHECK(slot_stride >= num_splits, "slot_stride must hold n * num_splits partials");
+    gp = groups->data_ptr<int>();
+    stride = slot_stride;
+  }
+  check_type(part_o, torch::kFloat32, "partial_o");
+  check_type(part_ml, torch::kFloat32, "partial_ml");
+  TORCH_CHECK(num_splits >= 1 && part_o.numel() >= B * Hq * stride * D && part_ml.numel() >= B * Hq * stride * 4,
+              "split workspace too small");
+  check_type(counters, torch::kInt32, "counters");
+  TORCH_CHECK(counters.numel() >= B * k_cache.size(1), "split counters too small");
+  const int* pp = nullptr;
+  if (plan.has_value() && plan->defined()) {
+    check_type(*plan, torch::kInt32, "plan");
+    TORCH_CHECK(plan_stride > attn_plan_hdr() && plan->numel() >= B * num_splits * plan_stride, "attention plan too small");
+    pp = plan->data_ptr<int>();
+  }
+  const int rc = launch_paged_decode_fp8(out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                         block_tables.data_ptr<int>(), ctx_lens.data_ptr<int>(),
+                                         part_o.data_ptr<float>(), part_ml.data_ptr<float>(), counters.data_ptr<int>(),
+                                         (int)B, (int)Hq, (int)k_cache.size(1), (int)D, (int)block_tables.size(1),
+                                         (float)scale, (int)num_splits, gp, (int)stride, cur_stream(), pp,
+                                         (int)plan_stride, (float)k_scale, (float)v_scale);
+  TORCH_CHECK(rc == 0, "paged_attention_decode (fp8 KV): unsupported configuration (rc=", rc, ")");
+}
+
+// tile_map [n, 2] (whole tiles; cmap / partials absent) or key-split items [n, 5] + cmap [m, 4] + partials
+void prefill_attention_fp8(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
+                           torch::Tensor block_tables, torch::Tensor cu_q, torch::Tensor start_pos,
+                           torch::Tensor tile_map, double scale, double k_scale, double v_scale,
+                           c10::optional<torch::Tensor> cmap, c10::optional<torch::Tensor> part_o,
+                           c10::optional<torch::Tensor> part_ml, int64_t n_parts) {
+  check_bf16(out, "out");
+  check_bf16(q, "q");
+  TORCH_CHECK(q.dim() == 3 && k_cache.dim() == 4, "q must be [T, Hq, D], caches 4-D");
+  const int64_t Hq = q.size(1), D = q.size(2), Hkv = k_cache.size(1);
+  check_caches(k_cache, v_cache, Hkv, D, true);
+  check_kv_scales(k_scale, v_scale, "prefill_attention (fp8 KV)");
+  TORCH_CHECK(k_cache.size(2) == 32, "prefill kernel requires kv block_size == 32");
+  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0 && prefill_split_supported((int)(Hq / Hkv), (int)D),
+              "prefill_attention: kv_dtype fp8 needs head_dim 128 and a GQA group <= 8 (the 32x32 kernel)");
+  check_type(block_tables, torch::kInt32, "block_tables");
+  check_type(cu_q, torch::kInt32, "cu_q");
+  check_type(start_pos, torch::kInt32, "start_pos");
+  check_type(tile_map, torch::kInt32, "tile_map");
+  TORCH_CHECK(block_tables.size(0) == cu_q.numel() - 1 && start_pos.numel() == cu_q.numel() - 1, "varlen metadata");
+  const bool split = cmap.has_value() && cmap->defined();
+  TORCH_CHECK(tile_map.dim() == 2 && tile_map.size(1) == (split ? 5 : 2), "tile_map must be [n, 2] or items [n, 5]");
+  const int* cp = nullptr;
+  float *po = nullptr, *pm = nullptr;
+  int n_split = 0;
+  if (split) {
+    check_type(*cmap, torch::kInt32, "cmap");
+    TORCH_CHECK(cmap->dim() == 2 && cmap->size(1) == 4, "cmap must be [m, 4]");
+    TORCH_CHECK(part_o.has_value() && part_ml.has_value(), "key-split prefill needs its partial buffers");
+    check_type(*part_o, torch::kFloat32, "part_o");
+    check_type(*part_ml, torch::kFloat32, "part_ml");
+    TORCH_CHECK(part_o->numel() >= n_parts * Hkv * 8 * 32 * D && part_ml->numel() >= n_parts * Hkv * 8 * 32 * 2,
+                "partial buffers too small");
+    cp = cmap->data_ptr<int>();
+    po = part_o->data_ptr<float>();
+    pm = part_ml->data_ptr<float>();
+    n_split = (int)cmap->size(0);
+  }
+  const int rc = launch_prefill_fp8(out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                    block_tables.data_ptr<int>(), cu_q.data_ptr<int>(), start_pos.data_ptr<int>(),
+                                    tile_map.data_ptr<int>(), (int)tile_map.size(0), split ? 5 : 2, cp, n_split, po, pm,
+                                    (int)Hq, (int)Hkv, (int)D, (int)block_tables.size(1), (float)scale, (float)k_scale,
+                                    (float)v_scale, cur_stream());
+  TORCH_CHECK(rc == 0, "prefill_attention (fp8 KV): unsupported configuration (rc=", rc, ")");
+}
+
+// The ROPE-epilogue qkv GEMM writing an fp8 cache; wscale: none = bf16 weights, fp32 = fp8 weights,
+// uint8 = mxfp4 weights (x2 / xout / split_ws: bf16 weights only)
+void skinny_gemm_rope_kv8(torch::Tensor q_out, torch::Tensor x, torch::Tensor W, c10::optional<torch::Tensor> wscale,
+                          int64_t pro, torch::Tensor positions, torch::Tensor cos_sin, torch::Tensor k_cache,
+                          torch::Tensor v_cache, torch::Tensor slots, int64_t Hq, int64_t Hkv, int64_t D, double eps,
+                          c10::optional<torch::Tensor> x2, c10::optional<torch::Tensor> xout,
+                          c10::optional<torch::Tensor> split_ws, int64_t split_mode,
+                          c10::optional<torch::Tensor> bias, double k_scale, double v_scale) {
+  const char* who = "skinny_gemm_rope (fp8 KV)";
+  check_bf16(q_out, "q_out");
+  check_bf16(x, "x");
+  TORCH_CHECK(x.dim() == 2, who, ": x [M, K]");
+  const int64_t M = x.size(0), K = x.size(1), N = (Hq + 2 * Hkv) * D;
+  check_kv_scales(k_scale, v_scale, who);
+  TORCH_CHECK(D > 0 && D % 64 == 0, who, ": head_dim must be a multiple of 64");
+  int wt = 0;
+  const void* ws = nullptr;
+  std::pair<const void*, void*> addo{nullptr, nullptr};
+  std::pair<int*, int64_t> sw{nullptr, 0};
+  if (!wscale.has_value() || !wscale->defined()) {
+    check_bf16(W, "Ws");
+    TORCH_CHECK(W.dim() == 2 && W.size(1) == K && W.size(0) == N, who, ": Ws must be [(Hq+2Hkv)*D, K]");
+    TORCH_CHECK(M >= 1 && M <= 32 && K % 32 == 0, who, ": 1 <= M <= 32, K % 32 == 0");
+    addo = add_operands(x, pro, x2, xout);
+    sw = split_workspace(split_ws, x);
+  } else {
+    TORCH_CHECK(!x2.has_value() && !xout.has_value() && !split_ws.has_value(), who,
+                ": quantised weights take no x2 / xout / split_ws");
+    TORCH_CHECK(M >= 1 && M <= 16, who, ": 1 <= M <= 16 on quantised weights");
+    TORCH_CHECK(pro == 0 || pro == 1, who, ": prologue PLAIN or NORM on quantised weights");
+    TORCH_CHECK(W.device() == x.device(), who, ": W and x on different devices");
+    if (wscale->scalar_type() == torch::kUInt8) {
+      wt = 2;
+      check_fp4_weight(W, *wscale, N, K, who);
+    } else {
+      wt = 1;
+      check_fp8_weight(W, *wscale, N, K, who);
+    }
+    ws = wscale->data_ptr();
+  }
+  const float* bp = rope_operands(who, q_out, x, M, positions, cos_sin, k_cache, v_cache, slots, Hq, Hkv, D, bias, true);
+  TORCH_CHECK(k_cache.size(2) % 8 == 0, who, ": block_size must be a multiple of 8");
+  const int rc = launch_skinny_gemm_rope_kv8(wt, q_out.data_ptr(), x.data_ptr(), W.data_ptr(), ws, (int)M, (int)K,
+                                             (int)pro, (float)eps, positions.data_ptr<int64_t>(),
+                                             cos_sin.data_ptr<float>(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                             slots.data_ptr<int64_t>(), (int)Hq, (int)Hkv, (int)D, (int)k_cache.size(2),
+                                             addo.first, addo.second, cur_stream(), sw.first, sw.second,
+                                             (int)split_mode, bp, (float)k_scale, (float)v_scale);
+  TORCH_CHECK(rc == 0, who, ": unsupported configuration (rc=", rc, ")");
+}
 }  // namespace
 
 PYBIND11_MODULE(_C, m) {
+  m.def("rope_and_cache_fp8", &rope_and_cache_fp8, "K2 with an fp8 (e4m3fn) K/V cache", py::arg("q_out"),
+        py::arg("qkv"), py::arg("positions"), py::arg("cos_sin"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("slots"), py::arg("Hq"), py::arg("Hkv"), py::arg("D"), py::arg("k_scale") = 1.0,
+        py::arg("v_scale") = 1.0);
+  m.def("paged_attention_decode_fp8", &paged_attention_decode_fp8, "K3 over an fp8 (e4m3fn) K/V cache",
+        py::arg("out"), py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("block_tables"),
+        py::arg("ctx_lens"), py::arg("scale"), py::arg("num_splits"), py::arg("part_o"), py::arg("part_ml"),
+        py::arg("counters"), py::arg("groups") = py::none(), py::arg("slot_stride") = 0,
+        py::arg("plan") = py::none(), py::arg("plan_stride") = 0, py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0);
+  m.def("prefill_attention_fp8", &prefill_attention_fp8, "K4 (32x32) over an fp8 (e4m3fn) K/V cache",
+        py::arg("out"), py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("block_tables"), py::arg("cu_q"),
+        py::arg("start_pos"), py::arg("tile_map"), py::arg("scale"), py::arg("k_scale") = 1.0,
+        py::arg("v_scale") = 1.0, py::arg("cmap") = py::none(), py::arg("part_o") = py::none(),
+        py::arg("part_ml") = py::none(), py::arg("n_parts") = 0);
+  m.def("skinny_gemm_rope_kv8", &skinny_gemm_rope_kv8,
+        "qkv decode GEMM (bf16 / fp8 / mxfp4 weights) with fused RoPE + fp8 K/V cache write", py::arg("q_out"),
+        py::arg("x"), py::arg("W"), py::arg("wscale"), py::arg("pro"), py::arg("positions"), py::arg("cos_sin"),
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("slots"), py::arg("Hq"), py::arg("Hkv"), py::arg("D"),
+        py::arg("eps") = 1e-5, py::arg("x2") = py::none(), py::arg("xout") = py::none(),
+        py::arg("split_ws") = py::none(), py::arg("split_mode") = 3, py::arg("bias") = py::none(),
+        py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0);
   m.def("skinny_gemm", &skinny_gemm, "decode GEMM (M<=16), shuffled weights, fused norm / resid / swiglu",
         py::arg("out"), py::arg("x"), py::arg("Ws"), py::arg("pro"), py::arg("epi"), py::arg("res") = py::none(),
         py::arg("eps") = 1e-5, py::arg("x2") = py::none(), py::arg("xout") = py::none(),

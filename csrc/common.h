@@ -87,6 +87,32 @@ RT_DEVICE void kc_chunk(int w, int BS, int& key, int& c) {
   c = c32 * 4 + (r & 3);
 }
 
+// ---- FP8 paged K/V layout (kv_dtype "fp8", one byte per element; kv_fp8_core.h is the scalar
+// rule). The tensors keep their [NB, Hkv, BS, D] / [NB, Hkv, D, BS] shapes with a one-byte dtype;
+// every fp8 writer and reader goes through these helpers (ops/reference.py mirrors them).
+// K blocks are 64-DIM-CHUNK-major, [D/64][BS keys][64 dims]: a lane's 16 B is 16 consecutive dims
+// of one key (two MFMA A fragments), and a decode load instruction (16 keys x 4 lane groups x 16 B)
+// again reads 8 whole 128-B lines, in 4-key runs of 256 B, as the bf16 chunk-major block does.
+RT_HD int kc8_elem(int BS, int key, int d) { return (d >> 6) * (BS * 64) + key * 64 + (d & 63); }
+// flat 16-B chunk w of one fp8 K block -> (key, 16-dim chunk c of that key's D-row)
+RT_HD void kc8_chunk(int w, int BS, int& key, int& c) {
+  const int c64 = w / (BS * 4), r = w - c64 * (BS * 4);
+  key = r >> 2;
+  c = c64 * 4 + (r & 3);
+}
+// V blocks: [D/32][16 dims r][BS/8 key groups g][2 dims u][8 keys], d = 32e + 16u + r, key = 8g + j:
+// a lane's 16 B is keys 8g..8g+7 of dims 32e + r and 32e + 16 + r (two MFMA B fragments of P.V),
+// and a load instruction (16 r x 4 g x 16 B, BS = 32) reads 1 KiB contiguous.
+RT_HD int vc8_elem(int BS, int key, int d) {
+  return (d >> 5) * (32 * BS) + (d & 15) * (2 * BS) + (key >> 3) * 16 + ((d >> 4) & 1) * 8 + (key & 7);
+}
+// flat 16-B chunk w of one fp8 V block (BS = 32) -> (first dim d0, key group g): bytes 0..7 are
+// keys 8g..8g+7 of dim d0, bytes 8..15 the same keys of dim d0 + 16
+RT_HD void vc8_chunk(int w, int& d0, int& g) {
+  d0 = (w >> 6) * 32 + ((w >> 2) & 15);
+  g = w & 3;
+}
+
 // ---- cross-workgroup hand-off I/O (MI355X_MICROARCH "Valid forms": every handed-off byte
 // stored sc1 (write-through past the XCD L2) and loaded sc1 (L1-bypassing), 16 B per lane).
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -99,6 +125,18 @@ RT_DEVICE float4_ sc1_load4(__amdgpu_buffer_rsrc_t r, int byte_off) {
 }
 RT_DEVICE void sc1_store4(__amdgpu_buffer_rsrc_t r, int byte_off, float4_ v) {
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, byte_off, 0, kSC1);
+}
+
+// bytes 8u .. 8u+7 of a 16-B register of e4m3fn codes (an fp8 K/V cache) as a bf16 MFMA fragment:
+// one v_cvt_scalef32_pk_bf16_fp8 per pair, exact (every e4m3 value is a bf16 value)
+RT_DEVICE bf16x8 kv8_frag(const short8& w, int u) {
+  const u32x4 c = __builtin_bit_cast(u32x4, w);
+  const unsigned lo = u ? c[2] : c[0], hi = u ? c[3] : c[1];
+  const bf16x2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false);
+  const bf16x2_t p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true);
+  const bf16x2_t p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false);
+  const bf16x2_t p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true);
+  return bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
 }
 
 }  // namespace rt

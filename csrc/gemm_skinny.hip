@@ -28,21 +28,22 @@ using rt::short8;
 using namespace skinny;
 
 // one tile per workgroup; WT_FP8 / WT_FP4: e4m3 / e2m1 weight codes, dequantised in registers (skinny_core.h)
-template <int PRO, int EPI, int NW, int U, int WT = WT_BF16>
+// KV8 (every wrapper below, EPI_ROPE only): the K/V caches are fp8 (skinny_core.h st_kv8)
+template <int PRO, int EPI, int NW, int U, int WT = WT_BF16, bool KV8 = false>
 __global__ void __launch_bounds__(NW * 64) skinny_gemm_kernel(GemmArgs p) {
   __shared__ GemmSmem<nacc<EPI>(), NW> sm;
   Stage<PRO, EPI, U, WT> st0;
-  gemm_tile<PRO, EPI, NW, U, false, false, -1, WT>(p, blockIdx.x, sm, st0, false, blockIdx.x == 0);
+  gemm_tile<PRO, EPI, NW, U, false, false, -1, WT, KV8>(p, blockIdx.x, sm, st0, false, blockIdx.x == 0);
 }
 
 // TN tiles per workgroup (skinny_core.h gemm_tiles): serving batches, M > 4
-template <int PRO, int EPI, int NW, int U, int TN, int MB = 1>
+template <int PRO, int EPI, int NW, int U, int TN, int MB = 1, bool KV8 = false>
 __global__ void __launch_bounds__(NW * 64) skinny_gemm_multi_kernel(GemmArgs p) {
   // two row blocks x (gate + up) x 4 tiles would not fit the static LDS: that variant is never
   // launched (the plan caps SwiGLU at 2 tiles with two row blocks), compiled as 2 tiles
   constexpr int TNX = (MB == 2 && nacc<EPI>() == 2 && TN > 2) ? 2 : TN;
   __shared__ GemmSmemN<nacc<EPI>(), NW, TNX, MB> sm;
-  gemm_tiles<PRO, EPI, NW, U, TNX, MB>(p, blockIdx.x * TNX, sm);
+  gemm_tiles<PRO, EPI, NW, U, TNX, MB, KV8>(p, blockIdx.x * TNX, sm);
 }
 
 
@@ -54,12 +55,13 @@ RT_DEVICE ALds alds_view(int kspan) {
 
 // The same launch with the A operand staged in LDS (skinny_core.h ALDS): tensor-parallel shard
 // shapes, where the per-k-step activation loads, not HBM, bound the launch.
-template <int PRO, int EPI, int NW, int U>
+template <int PRO, int EPI, int NW, int U, bool KV8 = false>
 __global__ void __launch_bounds__(NW * 64) skinny_gemm_alds_kernel(GemmArgs p) {
   __shared__ GemmSmem<nacc<EPI>(), NW> sm;
   Stage<PRO, EPI, U> st0;
   const ALds al = alds_view(p.K);
-  gemm_tile<PRO, EPI, NW, U, false, true>(p, blockIdx.x, sm, st0, false, blockIdx.x == 0, nullptr, &al);
+  gemm_tile<PRO, EPI, NW, U, false, true, -1, WT_BF16, KV8>(p, blockIdx.x, sm, st0, false, blockIdx.x == 0, nullptr,
+                                                            &al);
 }
 
 // CU-balanced launch for tile counts that are not a multiple of the CU count (gate_up of
@@ -70,7 +72,7 @@ __global__ void __launch_bounds__(NW * 64) skinny_gemm_alds_kernel(GemmArgs p) {
 // hand-offs finish under the whole tiles' streams), [2R, T + R) the whole tiles.
 // tools/exp_balance.hip: swiglu 768 / 896 / 1024 tiles = 31.0 / 37.6 / 40.5 us (896 is 1.8 us
 // above the line through its neighbours).
-template <int PRO, int EPI, int NW, int U>
+template <int PRO, int EPI, int NW, int U, bool KV8 = false>
 __global__ void __launch_bounds__(NW * 64) skinny_gemm_bal_kernel(GemmArgs p, int* __restrict__ ws, int R, int xpair) {
   __shared__ GemmSmem<nacc<EPI>(), NW> sm;
   Stage<PRO, EPI, U> st0;
@@ -88,9 +90,9 @@ __global__ void __launch_bounds__(NW * 64) skinny_gemm_bal_kernel(GemmArgs p, in
       idx = b & 1;
     }
     const SplitX sx{reinterpret_cast<float*>(ws + SPLIT_CTRS) + (size_t)r * 2 * SPLIT_STRIDE, ws + r, idx, 2};
-    gemm_tile<PRO, EPI, NW, U, false>(p, T - R + r, sm, st0, false, false, &sx);
+    gemm_tile<PRO, EPI, NW, U, false, false, -1, WT_BF16, KV8>(p, T - R + r, sm, st0, false, false, &sx);
   } else {
-    gemm_tile<PRO, EPI, NW, U, false>(p, b - 2 * R, sm, st0, false, false);
+    gemm_tile<PRO, EPI, NW, U, false, false, -1, WT_BF16, KV8>(p, b - 2 * R, sm, st0, false, false);
   }
 }
 
@@ -101,7 +103,7 @@ __global__ void __launch_bounds__(NW * 64) skinny_gemm_bal_kernel(GemmArgs p, in
 // Placement (speed only, never correctness): with T % 8 == 0 the S parts of a tile get block ids
 // b, b + 8, ... — one XCD under round-robin dispatch, so the combine reads same-XCD partials.
 // NORM_ADD: every part of tile 0 publishes its K range of x + x2.
-template <int PRO, int EPI, int NW, int U, bool ALDS = false>
+template <int PRO, int EPI, int NW, int U, bool ALDS = false, bool KV8 = false>
 __global__ void __launch_bounds__(NW * 64) skinny_gemm_splitk_kernel(GemmArgs p, int* __restrict__ ws, int S) {
   __shared__ GemmSmem<nacc<EPI>(), NW> sm;
   Stage<PRO, EPI, U> st0;
@@ -120,15 +122,15 @@ __global__ void __launch_bounds__(NW * 64) skinny_gemm_splitk_kernel(GemmArgs p,
   if constexpr (ALDS) {
     const int ks = p.K / 32;
     const ALds al = alds_view(32 * ((ks + S - 1) / S + 1));
-    gemm_tile<PRO, EPI, NW, U, false, true>(p, tile, sm, st0, false, tile == 0, &sx, &al);
+    gemm_tile<PRO, EPI, NW, U, false, true, -1, WT_BF16, KV8>(p, tile, sm, st0, false, tile == 0, &sx, &al);
   } else {
-    gemm_tile<PRO, EPI, NW, U, false>(p, tile, sm, st0, false, tile == 0, &sx);
+    gemm_tile<PRO, EPI, NW, U, false, false, -1, WT_BF16, KV8>(p, tile, sm, st0, false, tile == 0, &sx);
   }
 }
 
 // TN tiles per workgroup (gemm_tiles) with each group of TN tiles' K range cut into S parts (SplitX hand-off; group ids dealt as
 // in skinny_gemm_splitk_kernel, so a group's parts share an XCD under round-robin dispatch)
-template <int PRO, int EPI, int NW, int U, int TN, int MB = 1>
+template <int PRO, int EPI, int NW, int U, int TN, int MB = 1, bool KV8 = false>
 __global__ void __launch_bounds__(NW * 64) skinny_gemm_multi_split_kernel(GemmArgs p, int* __restrict__ ws, int S) {
   __shared__ GemmSmemN<nacc<EPI>(), NW, TN, MB> sm;
   const int G = (p.N / 16 + TN - 1) / TN;
@@ -144,7 +146,7 @@ __global__ void __launch_bounds__(NW * 64) skinny_gemm_multi_split_kernel(GemmAr
   }
   const SplitX sx{reinterpret_cast<float*>(ws + SPLIT_CTRS) + (size_t)grp * S * TN * MB * SPLIT_STRIDE, ws + grp, part,
                   S};
-  gemm_tiles<PRO, EPI, NW, U, TN, MB>(p, grp * TN, sm, &sx);
+  gemm_tiles<PRO, EPI, NW, U, TN, MB, KV8>(p, grp * TN, sm, &sx);
 }
 
 int device_cus() {
@@ -195,12 +197,18 @@ int launch(void (*kernel)(P...), const SkinnyPlan& pl, hipStream_t stream, A... 
   return hipGetLastError() == hipSuccess ? 0 : -6;
 }
 
-template <int WT>
+// KV8: the ROPE epilogue writes an fp8 K/V cache (any other epilogue with it is -2)
+template <int WT, bool KV8 = false>
 int launch_plan(const SkinnyPlan& pl, const GemmArgs& args, int pro, int epi, int* ws, hipStream_t stream) {
+  if constexpr (KV8) {
+    if (epi != EPI_ROPE) return -2;
+  }
+  // the kernels of an fp8 cache exist for the ROPE epilogue only
+#define RT_KV8(E) (KV8 && (E) == EPI_ROPE)
   switch (pl.form) {
     case ONE_TILE:
       return with_pro_epi<ONE_TILE, WT>(pro, epi, [&](auto P, auto E) {
-        const auto go = [&](auto v) { return launch(skinny_gemm_kernel<P(), E(), v.NW, v.U, WT>, pl, stream, args); };
+        const auto go = [&](auto v) { return launch(skinny_gemm_kernel<P(), E(), v.NW, v.U, WT, RT_KV8(E())>, pl, stream, args); };
         if constexpr (WT == WT_FP8)
           return with_variant<V<4, 2>, V<4, 4>>(pl, go);
         else if constexpr (WT == WT_FP4)
@@ -211,32 +219,37 @@ int launch_plan(const SkinnyPlan& pl, const GemmArgs& args, int pro, int epi, in
     case ALDS:
       return with_pro_epi<ALDS, WT>(pro, epi, [&](auto P, auto E) {
         return with_variant<V<4, 2>, V<16, 2>, V<8, 2>, V<4, 8>, V<8, 4>, V<8, 8>, V<4, 4>>(
-            pl, [&](auto v) { return launch(skinny_gemm_alds_kernel<P(), E(), v.NW, v.U>, pl, stream, args); });
+            pl, [&](auto v) { return launch(skinny_gemm_alds_kernel<P(), E(), v.NW, v.U, RT_KV8(E())>, pl, stream, args); });
       });
     case SPLITK:
       return with_pro_epi<SPLITK, WT>(pro, epi, [&](auto P, auto E) {
-        if (pl.alds) return launch(skinny_gemm_splitk_kernel<P(), E(), 8, 2, true>, pl, stream, args, ws, pl.S);
+        if (pl.alds) return launch(skinny_gemm_splitk_kernel<P(), E(), 8, 2, true, RT_KV8(E())>, pl, stream, args, ws, pl.S);
         return with_variant<V<4, 2>, V<4, 4>, V<8, 2>>(
-            pl, [&](auto v) { return launch(skinny_gemm_splitk_kernel<P(), E(), v.NW, v.U>, pl, stream, args, ws, pl.S); });
+            pl, [&](auto v) {
+              return launch(skinny_gemm_splitk_kernel<P(), E(), v.NW, v.U, false, RT_KV8(E())>, pl, stream, args, ws,
+                            pl.S);
+            });
       });
     case MULTI:
       return with_pro_epi<MULTI, WT>(pro, epi, [&](auto P, auto E) {
         return with_variant<V<4, 2, 4, 2>, V<4, 2, 2, 2>, V<4, 2, 1, 2>, V<8, 2, 2>, V<4, 4, 2>, V<4, 2, 2>, V<8, 2, 4>,
                             V<4, 2, 4>>(pl, [&](auto v) {
-          return launch(skinny_gemm_multi_kernel<P(), E(), v.NW, v.U, v.TN, v.MB>, pl, stream, args);
+          return launch(skinny_gemm_multi_kernel<P(), E(), v.NW, v.U, v.TN, v.MB, RT_KV8(E())>, pl, stream, args);
         });
       });
     case MULTI_SPLIT:
       return with_pro_epi<MULTI_SPLIT, WT>(pro, epi, [&](auto P, auto E) {
         return with_variant<V<4, 2, 2, 2>, V<4, 2, 2>>(pl, [&](auto v) {
-          return launch(skinny_gemm_multi_split_kernel<P(), E(), v.NW, v.U, 2, v.MB>, pl, stream, args, ws, pl.S);
+          return launch(skinny_gemm_multi_split_kernel<P(), E(), v.NW, v.U, 2, v.MB, RT_KV8(E())>, pl, stream, args, ws,
+                        pl.S);
         });
       });
     case BALANCED:
       return with_pro_epi<BALANCED, WT>(pro, epi, [&](auto P, auto E) {
-        return launch(skinny_gemm_bal_kernel<P(), E(), 4, 2>, pl, stream, args, ws, pl.R, pl.xpair);
+        return launch(skinny_gemm_bal_kernel<P(), E(), 4, 2, RT_KV8(E())>, pl, stream, args, ws, pl.R, pl.xpair);
       });
   }
+#undef RT_KV8
   return -2;
 }
 
@@ -246,7 +259,7 @@ int launch_plan(const SkinnyPlan& pl, const GemmArgs& args, int pro, int epi, in
 // (SwiGLU: I).
 int launch_gemm(int wt, void* out, const void* x, const void* Ws, const void* wscale, void* res, int M, int N, int K,
                 int ldo, float eps, int pro, int epi, const void* rope, const void* x2, void* xo, hipStream_t stream,
-                int* split_ws, int64_t split_ws_ints, int split_mode) {
+                int* split_ws, int64_t split_ws_ints, int split_mode, bool kv8 = false) {
   const bool f8 = wt != WT_BF16;   // quantised weights, either type
   const int kd = wt == WT_FP4 ? kdeep<WT_FP4>() : (wt == WT_FP8 ? kdeep<WT_FP8>() : kdeep<WT_BF16>());
   if (!f8 && pro == PRO_NORM_ADD && x2 == nullptr) return -5;
@@ -261,6 +274,12 @@ int launch_gemm(int wt, void* out, const void* x, const void* Ws, const void* ws
     re = *static_cast<const RopeEpi*>(rope);
     // D % 32: the K write goes through kc_elem ([D/32][BS][32] chunks)
     if (re.D <= 0 || re.D % 32 || N != (re.Hq + 2 * re.Hkv) * re.D) return -4;
+    // an fp8 cache: the kc8_elem / vc8_elem block layouts, finite positive scales (-7)
+    if (kv8 && (re.D % 64 || re.BS <= 0 || re.BS % 8 || !(re.k_inv > 0.f) || !(re.v_inv > 0.f) ||
+                !(re.k_inv <= 3.0e38f) || !(re.v_inv <= 3.0e38f)))
+      return -7;
+  } else if (kv8) {
+    return -7;
   }
   const SkinnyPlan pl =
       plan_skinny_gemm(wt, M, N, K, pro, epi, device_cus(), split_ws != nullptr, split_ws_ints, split_mode, knobs());
@@ -270,9 +289,13 @@ int launch_gemm(int wt, void* out, const void* x, const void* Ws, const void* ws
   args.kmajor = resolve_order(N / 16, K, epi == EPI_SWIGLU, epi == EPI_ROPE);
   if (wt == WT_FP4) {
     args.bscale = static_cast<const uint8_t*>(wscale);
-    return launch_plan<WT_FP4>(pl, args, pro, epi, split_ws, stream);
+    return kv8 ? launch_plan<WT_FP4, true>(pl, args, pro, epi, split_ws, stream)
+               : launch_plan<WT_FP4>(pl, args, pro, epi, split_ws, stream);
   }
   args.wscale = static_cast<const float*>(wscale);
+  if (kv8)
+    return f8 ? launch_plan<WT_FP8, true>(pl, args, pro, epi, split_ws, stream)
+              : launch_plan<WT_BF16, true>(pl, args, pro, epi, split_ws, stream);
   return f8 ? launch_plan<WT_FP8>(pl, args, pro, epi, split_ws, stream)
             : launch_plan<WT_BF16>(pl, args, pro, epi, split_ws, stream);
 }
@@ -357,6 +380,26 @@ int launch_skinny_gemm_rope_fp4(void* q_out, const void* x, const void* Wq, cons
   const RopeEpi re{positions, cos_sin, (uint16_t*)k_cache, (uint16_t*)v_cache, slots, Hq, Hkv, D, BS, bias};
   return launch_skinny_gemm_fp4(q_out, x, Wq, scale, nullptr, M, (Hq + 2 * Hkv) * D, K, 0, eps, pro, EPI_ROPE, &re,
                                 stream);
+}
+
+// The ROPE-epilogue qkv GEMM writing an fp8 K/V cache (kv_dtype "fp8": e4m3fn bytes, value = code *
+// scale; common.h kc8_elem / vc8_elem), for all three weight types from the one epilogue: wt = 0
+// bf16 (W shuffled, wscale null), 1 fp8 (wscale: fp32 row scales), 2 mxfp4 (wscale: e8m0 bytes).
+// x2 / xo / the split workspace: bf16 weights only. -7: scale or cache shape, before any HIP call.
+int launch_skinny_gemm_rope_kv8(int wt, void* q_out, const void* x, const void* W, const void* wscale, int M, int K,
+                                int pro, float eps, const int64_t* positions, const float* cos_sin, void* k_cache,
+                                void* v_cache, const int64_t* slots, int Hq, int Hkv, int D, int BS, const void* x2,
+                                void* xo, hipStream_t stream, int* split_ws, int64_t split_ws_ints, int split_mode,
+                                const float* bias, float k_scale, float v_scale) {
+  if (wt != WT_BF16 && wt != WT_FP8 && wt != WT_FP4) return -1;
+  if (!(k_scale > 0.f) || !(v_scale > 0.f) || !(k_scale <= 3.0e38f) || !(v_scale <= 3.0e38f)) return -7;
+  RopeEpi re{positions, cos_sin, (uint16_t*)k_cache, (uint16_t*)v_cache, slots, Hq, Hkv, D, BS, bias};
+  re.k_inv = 1.f / k_scale;
+  re.v_inv = 1.f / v_scale;
+  const bool bf = wt == WT_BF16;
+  return launch_gemm(wt, q_out, x, W, wscale, nullptr, M, (Hq + 2 * Hkv) * D, K, 0, eps, pro, EPI_ROPE, &re,
+                     bf ? x2 : nullptr, bf ? xo : nullptr, stream, bf ? split_ws : nullptr, bf ? split_ws_ints : 0,
+                     bf ? split_mode : 0, true);
 }
 
 int launch_shuffle_weight(void* Ws, const void* W, const void* gamma, int N, int K, int rope_rows, int D, int swiglu,

@@ -19,7 +19,9 @@ __global__ void __launch_bounds__(256) kv_block_copy_kernel(uint16_t* __restrict
 }
 }  // namespace
 
-// k, v: [L, NB, block_elems] bf16; src/dst: device int32 [n]. block_elems % 8 == 0.
+// k, v: [L, NB, block_elems] in 2-byte units (bf16 elements; an fp8 pool passes half its bytes
+// per block: the copy moves bytes, whatever they encode); src/dst: device int32 [n].
+// block_elems % 8 == 0.
 int launch_kv_block_copy(void* k, void* v, const int* src, const int* dst, int n, int L, int num_blocks,
                          int64_t block_elems, hipStream_t stream) {
   if (n <= 0) return 0;

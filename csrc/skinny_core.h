@@ -52,6 +52,7 @@
 // range (a quarter of the records; k-major stays one record).
 #pragma once
 #include "common.h"
+#include "kv_fp8_core.h"
 
 namespace skinny {
 using rt::bf16x8;
@@ -75,7 +76,16 @@ struct RopeEpi {
   const int64_t* slots;      // [M]
   int Hq, Hkv, D, BS;
   const float* bias;         // [N] q/k/v bias in the epilogue's column order (Qwen2), or null
+  // fp8 K/V cache (the KV8 instantiations only; kv_fp8_core.h): 1 / k_scale, 1 / v_scale. The
+  // caches then hold one e4m3fn byte per element in the layouts of common.h kc8_elem / vc8_elem.
+  float k_inv = 1.f, v_inv = 1.f;
 };
+
+// EPI_ROPE with an fp8 cache: the finished fp32 sum (after bias and RoPE) leaves as one code byte,
+// a plain vector byte store, one per thread
+RT_DEVICE void st_kv8(uint16_t* cache, size_t byte_off, float y, float inv_scale) {
+  reinterpret_cast<uint8_t*>(cache)[byte_off] = (uint8_t)kv_fp8_code(y, inv_scale);
+}
 
 // EPI_AR: the K9 comm of csrc/oneshot_ar.hip (receive buffers [2 slots][world][cap] bf16 and
 // per-tile flags [2][world][maxt] of every rank, the comm's call counter [epoch, done])
@@ -671,7 +681,9 @@ RT_DEVICE void ar_exchange(const GemmArgs& p, int tile, float v, int m, int n, b
 // AC (persistent kernels): coherence of the ACTIVATION loads apart from the stores — -1 = as SC1,
 // 0 = plain (the activation came from an earlier launch), 1 = sc1 (produced in this launch). With
 // ALDS, AC = 1 stages the rows with sc1 loads once, then reads LDS.
-template <int PRO, int EPI, int NW, int U, bool SC1, bool ALDS = false, int AC = -1, int WT = WT_BF16>
+// KV8 (EPI_ROPE only): the K/V caches are fp8 (RopeEpi::k_inv / v_inv, st_kv8).
+template <int PRO, int EPI, int NW, int U, bool SC1, bool ALDS = false, int AC = -1, int WT = WT_BF16,
+          bool KV8 = false>
 RT_DEVICE void gemm_tile(const GemmArgs& p, int tile, GemmSmem<nacc<EPI>(), NW>& sm, Stage<PRO, EPI, U, WT>& st0,
                          bool prefetched,
                          bool publish_xo, const SplitX* sx = nullptr, const ALds* al = nullptr) {
@@ -863,13 +875,24 @@ RT_DEVICE void gemm_tile(const GemmArgs& p, int tile, GemmSmem<nacc<EPI>(), NW>&
         // pair (x1 = d i, x2 = d i+D/2): y1 = x1 c - x2 s ; y2 = x2 c + x1 s
         const float y = hi ? fmaf(v, c, partner * sn) : fmaf(v, c, -partner * sn);
         const int d = i + hi * half;
-        uint16_t* dst = (h < re.Hq) ? p.out + ((size_t)m * re.Hq + h) * D + d
-                                    : re.k_cache + ((size_t)blk * re.Hkv + (h - re.Hq)) * re.BS * D +
-                                          rt::kc_elem(re.BS, off, d);
-        st16<SC1>(dst, y);
+        if constexpr (KV8) {
+          if (h < re.Hq)
+            st16<SC1>(p.out + ((size_t)m * re.Hq + h) * D + d, y);
+          else
+            st_kv8(re.k_cache, ((size_t)blk * re.Hkv + (h - re.Hq)) * re.BS * D + rt::kc8_elem(re.BS, off, d), y,
+                   re.k_inv);
+        } else {
+          uint16_t* dst = (h < re.Hq) ? p.out + ((size_t)m * re.Hq + h) * D + d
+                                      : re.k_cache + ((size_t)blk * re.Hkv + (h - re.Hq)) * re.BS * D +
+                                            rt::kc_elem(re.BS, off, d);
+          st16<SC1>(dst, y);
+        }
       } else {
         const int hv = h - re.Hq - re.Hkv;
-        st16<SC1>(re.v_cache + (((size_t)blk * re.Hkv + hv) * D + pp) * re.BS + off, v);
+        if constexpr (KV8)
+          st_kv8(re.v_cache, ((size_t)blk * re.Hkv + hv) * D * re.BS + rt::vc8_elem(re.BS, off, pp), v, re.v_inv);
+        else
+          st16<SC1>(re.v_cache + (((size_t)blk * re.Hkv + hv) * D + pp) * re.BS + off, v);
       }
     } else if constexpr (EPI == EPI_AR) {
       // stored after the exchange below
@@ -961,7 +984,7 @@ RT_DEVICE void consume_n(const StageN<PRO, EPI, U, TN, MB>& st, float4_ (*acc)[M
 // sums are handed over as in gemm_tile (sx->part holds [n][TN][MB][SPLIT_STRIDE]) and the last
 // arrival sums the parts in index order and runs the epilogue — the o / down shapes (256 tiles)
 // keep a workgroup per CU while each workgroup reads the activations for two tiles.
-template <int PRO, int EPI, int NW, int U, int TN, int MB>
+template <int PRO, int EPI, int NW, int U, int TN, int MB, bool KV8 = false>
 RT_DEVICE void gemm_tiles(const GemmArgs& p, int tile0, GemmSmemN<nacc<EPI>(), NW, TN, MB>& sm,
                           const SplitX* sx = nullptr) {
   static_assert(PRO == PRO_PLAIN || PRO == PRO_NORM, "multi-tile launches: plain / norm prologues");
@@ -1177,13 +1200,24 @@ RT_DEVICE void gemm_tiles(const GemmArgs& p, int tile0, GemmSmemN<nacc<EPI>(), N
             const int i = pp >> 1, hi = pp & 1;
             const float y = hi ? fmaf(v, e_c[t][b], partner * e_s[t][b]) : fmaf(v, e_c[t][b], -partner * e_s[t][b]);
             const int d = i + hi * half;
-            uint16_t* dst = (h < re.Hq) ? p.out + ((size_t)row * re.Hq + h) * D + d
-                                        : re.k_cache + ((size_t)blk * re.Hkv + (h - re.Hq)) * re.BS * D +
-                                              rt::kc_elem(re.BS, off, d);
-            st16<false>(dst, y);
+            if constexpr (KV8) {
+              if (h < re.Hq)
+                st16<false>(p.out + ((size_t)row * re.Hq + h) * D + d, y);
+              else
+                st_kv8(re.k_cache, ((size_t)blk * re.Hkv + (h - re.Hq)) * re.BS * D + rt::kc8_elem(re.BS, off, d), y,
+                       re.k_inv);
+            } else {
+              uint16_t* dst = (h < re.Hq) ? p.out + ((size_t)row * re.Hq + h) * D + d
+                                          : re.k_cache + ((size_t)blk * re.Hkv + (h - re.Hq)) * re.BS * D +
+                                                rt::kc_elem(re.BS, off, d);
+              st16<false>(dst, y);
+            }
           } else {
             const int hv = h - re.Hq - re.Hkv;
-            st16<false>(re.v_cache + (((size_t)blk * re.Hkv + hv) * D + pp) * re.BS + off, v);
+            if constexpr (KV8)
+              st_kv8(re.v_cache, ((size_t)blk * re.Hkv + hv) * D * re.BS + rt::vc8_elem(re.BS, off, pp), v, re.v_inv);
+            else
+              st16<false>(re.v_cache + (((size_t)blk * re.Hkv + hv) * D + pp) * re.BS + off, v);
           }
         } else {
           st16<false>(p.out + (size_t)row * p.ldo + col, v);

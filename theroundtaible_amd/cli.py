@@ -678,7 +678,8 @@ def cmd_serve(args, ui: UI) -> int:
     srv = build_server(args.model, weights=args.weights, device=args.device, dtype=args.dtype, host=args.host,
                        port=args.port, max_batch=args.max_batch or (64 if tp <= 1 else 16), max_tokens=args.max_tokens,
                        use_graphs=not args.no_graphs, num_blocks=args.num_blocks, tp=tp,
-                       op_limit_s=float(args.op_timeout), weight_quant=getattr(args, "weight_quant", None))
+                       op_limit_s=float(args.op_timeout), weight_quant=getattr(args, "weight_quant", None),
+                       kv_dtype=getattr(args, "kv_dtype", None))
     if srv is None:            # a follower rank of serve --tp N: served rank 0 until shutdown
         return 0
     ui.ok(f"  ✓ {args.model} on {srv.engine.device}: {srv.engine.kv_capacity_tokens} KV tokens resident capacity")
@@ -780,6 +781,9 @@ def build_parser() -> argparse.ArgumentParser:
     sv.add_argument("--weight-quant", dest="weight_quant", choices=["none", "fp8", "mxfp4"], default=None,
                     help="weight-only quantisation of the decode linears (fp8: e4m3 codes + per-row scales; "
                          "mxfp4: e2m1 codes + one scale byte per 32 weights; tp 1, bf16 activations); default: ROUNDTABLE_WEIGHT_QUANT or none")
+    sv.add_argument("--kv-dtype", dest="kv_dtype", choices=["bf16", "fp8"], default=None,
+                    help="K/V page dtype (fp8: e4m3 codes, one byte per element, per-layer scales 1.0; twice the "
+                         "resident tokens; tp 1, head_dim 128, bf16 activations); default: ROUNDTABLE_KV_DTYPE or bf16")
     sv.add_argument("--host", default="127.0.0.1")
     sv.add_argument("--port", type=int, default=8000)
     sv.add_argument("--max-batch", type=int, default=None,

@@ -131,9 +131,58 @@ def resolve_weight_quant(value: Optional[str]) -> str:
     return q
 
 
+KV_DTYPES = ("bf16", "fp8")
+
+
+def resolve_kv_dtype(value: Optional[str]) -> str:
+    """A stated ``kv_dtype`` ("bf16" | "fp8"), or — when a config says nothing (None / "") — the
+    ROUNDTABLE_KV_DTYPE default, else "bf16". "fp8": K/V pages hold OCP e4m3fn codes, one byte per
+    element, with one fp32 k_scale and v_scale per layer (``kv_scale``)."""
+    q = str(value if value else os.environ.get("ROUNDTABLE_KV_DTYPE") or "bf16").lower()
+    if q == "bfloat16":
+        q = "bf16"
+    if q not in KV_DTYPES:
+        raise ConfigError(f"unknown kv_dtype {q!r}", hint=f"One of: {', '.join(KV_DTYPES)}.")
+    return q
+
+
+def per_layer_kv_scales(value, n_layers: int, which: str = "k") -> list:
+    """One KV scale per layer from one float or a list with one float per layer. The ONE Python copy of
+    the scale rule (the launchers repeat it in front of their kernels): every scale a finite number > 0
+    whose fp32 value and reciprocal are finite and normal; ConfigError naming kv_dtype otherwise."""
+    import math
+    vals = list(value) if isinstance(value, (list, tuple)) else [value] * n_layers
+    if len(vals) != n_layers:
+        raise ConfigError(f"kv_dtype: kv_scale.{which} has {len(vals)} values for {n_layers} layers",
+                          hint="One float, or a list with one float per layer.")
+    for s in vals:
+        if isinstance(s, bool) or not isinstance(s, (int, float)) or not math.isfinite(s) or s <= 0 \
+                or float(s) > 3.0e38 or float(s) < 1.2e-38:
+            raise ConfigError(f"kv_dtype: kv_scale.{which} must be finite and > 0 (got {s!r})")
+    return [float(s) for s in vals]
+
+
+def resolve_kv_scale(value, n_layers: Optional[int] = None) -> Dict[str, Any]:
+    """``kv_scale`` as ``{"k": x, "v": y}``, each one float or a list with one float per layer
+    (default 1.0), checked by :func:`per_layer_kv_scales` (``n_layers`` None: a list of any length)."""
+    if value is None:
+        value = {}
+    if not isinstance(value, dict) or set(value) - {"k", "v"}:
+        raise ConfigError("kv_dtype: kv_scale must be an object {\"k\": x, \"v\": y}",
+                          hint="Each of k / v is one float or a list with one float per layer.")
+    out = {}
+    for which in ("k", "v"):
+        x = value.get(which, 1.0)
+        is_list = isinstance(x, (list, tuple))
+        vals = per_layer_kv_scales(x, (len(x) if n_layers is None else n_layers) if is_list else 1, which)
+        out[which] = vals if is_list else vals[0]
+    return out
+
+
 def engine_settings(config: RoundtableConfig, adapter_id: str) -> Dict[str, Any]:
     """Effective engine settings for one adapter id: defaults <- config.engine <- adapter engine.
     ``weight_quant`` (engine-wide or per knight) comes back resolved: "none" | "fp8" | "mxfp4".
+    ``kv_dtype`` (engine-wide or per knight) comes back resolved: "bf16" | "fp8", ``kv_scale`` checked.
     ``consensus_grammar`` (engine-wide or per knight) is a bool; with ``scripted_consensus`` a ConfigError."""
     out = dict(ENGINE_DEFAULTS)
     top = config.raw.get("engine") if isinstance(config.raw, dict) else None
@@ -147,6 +196,12 @@ def engine_settings(config: RoundtableConfig, adapter_id: str) -> Dict[str, Any]
         out["model"] = resolve_model_name(ac.get("model") if isinstance(ac, dict) else None,
                                           out["default_model"])
     out["weight_quant"] = resolve_weight_quant(out.get("weight_quant"))
+    out["kv_dtype"] = resolve_kv_dtype(out.get("kv_dtype"))
+    # kv_scale is read (and checked) only with an fp8 cache: a stray one beside bf16 pages is passed on as is
+    if out["kv_dtype"] == "fp8":
+        out["kv_scale"] = resolve_kv_scale(out.get("kv_scale"))
+    else:
+        out["kv_scale"] = out.get("kv_scale") or {}
     if not isinstance(out.get("consensus_grammar", False), bool):
         raise ConfigError(f"{adapter_id}: engine.consensus_grammar must be true or false")
     if out.get("consensus_grammar") and out.get("scripted_consensus"):

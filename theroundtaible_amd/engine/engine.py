@@ -28,7 +28,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from .. import ops
-from ..config import resolve_weight_quant
+from ..config import resolve_kv_dtype, resolve_kv_scale, resolve_weight_quant
 from ..consensus import parse_consensus
 from ..errors import AdapterError, ConfigError, DeviceFlagError, EngineTimeout
 from ..models.config import ModelConfig, get_config
@@ -84,6 +84,15 @@ class EngineConfig:
     # csrc/gemm_skinny_fp4.hip), every semantic of "fp8" (``weight_residency`` "mxfp4").
     # Default: "none", or ROUNDTABLE_WEIGHT_QUANT when the caller states nothing
     weight_quant: str = field(default_factory=lambda: resolve_weight_quant(None))
+    # K/V page dtype: "bf16" | "fp8" (opt-in). "fp8": OCP e4m3fn codes, one byte per element, value =
+    # e4m3(code) * scale with one fp32 k_scale and v_scale per layer (``kv_scale``): the pool holds
+    # twice the tokens and decode attention streams half the bytes. tp 1, Llama / Mistral / Qwen2,
+    # head_dim 128, GQA group <= 8, bf16 activations on the GPU. Default: "bf16", or
+    # ROUNDTABLE_KV_DTYPE when the caller states nothing.
+    kv_dtype: str = field(default_factory=lambda: resolve_kv_dtype(None))
+    # {"k": x, "v": y}: each one float or a list with one float per layer (default 1.0); read only
+    # with kv_dtype "fp8". Values beyond 448 * scale saturate.
+    kv_scale: Dict[str, object] = field(default_factory=dict)
 
 
 @dataclass
@@ -132,6 +141,26 @@ class Engine:
                                   f"(tp={self.tp.size})", hint="Run the knight at tp 1 or drop weight_quant.")
             if self.on_gpu and self.dtype != torch.bfloat16:
                 raise ConfigError(f"{ecfg.model}: weight_quant={wq!r} needs dtype bf16 on the GPU (got {ecfg.dtype})")
+        self.kv_dtype = resolve_kv_dtype(ecfg.kv_dtype)
+        self.kv_scale = {"k": 1.0, "v": 1.0}
+        if self.kv_dtype == "fp8":
+            # refuse before any weight is loaded: never a silent bf16-KV run
+            who = f"{ecfg.model}: kv_dtype='fp8'"
+            if self.tp.size > 1:
+                raise ConfigError(f"{who} does not support tensor parallel (tp={self.tp.size})",
+                                  hint="Run the knight at tp 1 or drop kv_dtype.")
+            if self.cfg.arch == "gpt2":
+                raise ConfigError(f"{who} needs a Llama / Mistral / Qwen2 model, not {self.cfg.arch}")
+            if self.on_gpu and self.dtype != torch.bfloat16:
+                raise ConfigError(f"{who} needs dtype bf16 on the GPU (got {ecfg.dtype})")
+            G = self.cfg.n_heads // max(1, self.cfg.n_kv_heads)
+            if self.cfg.head_dim != 128 or G > 8:
+                raise ConfigError(f"{who} needs head_dim 128 and a GQA group <= 8 (got head_dim "
+                                  f"{self.cfg.head_dim}, group {G})",
+                                  hint="The fp8 K/V kernels exist for the 32x32 prefill kernel's shapes only.")
+            if ecfg.block_size != 32 and self.on_gpu:
+                raise ConfigError(f"{who} needs kv block_size 32 (got {ecfg.block_size})")
+            self.kv_scale = resolve_kv_scale(ecfg.kv_scale, self.cfg.n_layers)
         # the checkpoint's own tokenizer + chat template when `weights` ships one, else the bundled BPE
         self.tokenizer: EngineTokenizer = get_tokenizer(self.cfg.vocab, ecfg.weights, ecfg.chat_template)
         t0 = time.perf_counter()
@@ -207,7 +236,7 @@ class Engine:
         m = self.model
         bs = self.ecfg.block_size
         per_block = PagedKVCache.bytes_per_block(self.cfg.n_layers, m.kv_heads_local, self.cfg.head_dim, bs,
-                                                 torch.finfo(self.dtype).bits // 8)
+                                                 self._kv_elem_bytes())
         nb = self.ecfg.num_blocks
         if nb is None and self.ecfg.kv_budget_bytes is not None:
             nb = max(64, int(self.ecfg.kv_budget_bytes) // per_block)
@@ -226,8 +255,12 @@ class Engine:
             # them or none (a pool sized from one rank's free memory, e.g. a second rehearsal rank
             # on a shared GPU, could run out alone and skip collectives its peers enter)
             nb = self.tp.group_min(int(nb))
-        kv = PagedKVCache(self.cfg.n_layers, m.kv_heads_local, self.cfg.head_dim, int(nb), bs,
-                          self.device, self.dtype)
+        if self.kv_dtype == "fp8":
+            kv = PagedKVCache(self.cfg.n_layers, m.kv_heads_local, self.cfg.head_dim, int(nb), bs, self.device,
+                              torch.uint8, k_scale=self.kv_scale["k"], v_scale=self.kv_scale["v"])
+        else:
+            kv = PagedKVCache(self.cfg.n_layers, m.kv_heads_local, self.cfg.head_dim, int(nb), bs,
+                              self.device, self.dtype)
         kv.max_tokens = self.cfg.max_pos   # RoPE table / block-table width (_max_blocks)
         return kv
 
@@ -250,9 +283,13 @@ class Engine:
     def kv_allocated(self) -> bool:
         return self._kv is not None
 
+    def _kv_elem_bytes(self) -> int:
+        """Bytes per K/V element: 1 with kv_dtype "fp8", else the activation dtype's."""
+        return 1 if self.kv_dtype == "fp8" else torch.finfo(self.dtype).bits // 8
+
     def kv_bytes_per_token(self) -> int:
         return PagedKVCache.bytes_per_block(self.cfg.n_layers, self.model.kv_heads_local, self.cfg.head_dim, 1,
-                                            torch.finfo(self.dtype).bits // 8)
+                                            self._kv_elem_bytes())
 
     @property
     def kv_capacity_tokens(self) -> int:

@@ -18,6 +18,8 @@ from typing import Dict, List, Optional
 
 import torch
 
+from ..config import per_layer_kv_scales
+
 
 class KVCacheOOM(RuntimeError):
     """Raised when the block pool is exhausted (classified as ``oom`` by the orchestrator)."""
@@ -72,12 +74,22 @@ class SeqState:
 
 class PagedKVCache:
     def __init__(self, n_layers: int, n_kv_heads: int, head_dim: int, num_blocks: int, block_size: int,
-                 device, dtype=torch.bfloat16):
+                 device, dtype=torch.bfloat16, k_scale=1.0, v_scale=1.0):
+        """``dtype=torch.uint8``: an fp8 pool (kv_dtype "fp8"): one OCP e4m3fn code byte per element in
+        the fp8 block byte order (ops/reference.py ``k_blocks_fp8`` / ``v_blocks_fp8``), value =
+        e4m3(code) * scale with ``k_scale`` / ``v_scale`` one float or one per layer. Zero bytes are
+        +0, so the zero-init invariant below holds."""
         self.n_layers, self.n_kv_heads, self.head_dim = n_layers, n_kv_heads, head_dim
         self.block_size = block_size
         self.num_blocks = num_blocks
         self.device = device
         self.dtype = dtype
+        self.fp8 = dtype == torch.uint8
+        self.k_scales = per_layer_kv_scales(k_scale, n_layers, "k")
+        self.v_scales = per_layer_kv_scales(v_scale, n_layers, "v")
+        if self.fp8 and (head_dim % 64 or block_size % 8):
+            raise ValueError(f"kv_dtype fp8 needs head_dim % 64 == 0 and block_size % 8 == 0 "
+                             f"(got {head_dim}, {block_size})")
         shape = (n_layers, num_blocks, n_kv_heads, block_size * head_dim)
         # zero-init: masked tail keys of a partial block must be finite (0 * NaN = NaN in P.V)
         self.k = torch.zeros(shape, dtype=dtype, device=device)
@@ -91,6 +103,11 @@ class PagedKVCache:
 
     def v_layer(self, l: int) -> torch.Tensor:
         return self.v[l].view(self.num_blocks, self.n_kv_heads, self.head_dim, self.block_size)
+
+    def scales(self, l: int):
+        """(k_scale, v_scale) of layer ``l``: launch constants of the fp8 writers and attention
+        kernels (1.0, 1.0 and unread for a bf16 pool)."""
+        return self.k_scales[l], self.v_scales[l]
 
     @staticmethod
     def bytes_per_block(n_layers, n_kv_heads, head_dim, block_size, dtype_bytes=2) -> int:

@@ -8,10 +8,11 @@ orchestrator batches their knights into one decode (``group_key``).
 """
 from __future__ import annotations
 
+import json
 import threading
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
-from ..config import resolve_weight_quant
+from ..config import resolve_kv_dtype, resolve_weight_quant
 from ..consensus import consensus_grammar
 from ..engine.engine import Engine, EngineConfig, Turn
 from ..engine.sampler import SamplingParams
@@ -97,9 +98,11 @@ class EnginePool:
 
     def get(self, ecfg: EngineConfig, defer_kv: bool = False) -> Tuple[Engine, threading.Lock]:
         """``defer_kv``: load weights only; :meth:`finalize` sizes the KV pools afterwards."""
-        # (a bf16 knight and an fp8 knight of the same model never share an engine)
+        # (a bf16 knight and an fp8 knight of the same model never share an engine; nor do a
+        # bf16-KV knight and an fp8-KV knight, nor two fp8-KV knights with different scales)
         key = (ecfg.model, ecfg.weights, ecfg.dtype, ecfg.device, ecfg.block_size,
-               resolve_weight_quant(ecfg.weight_quant))
+               resolve_weight_quant(ecfg.weight_quant), resolve_kv_dtype(ecfg.kv_dtype),
+               json.dumps(ecfg.kv_scale, sort_keys=True) if resolve_kv_dtype(ecfg.kv_dtype) != "bf16" else "")
         if key not in self.engines:
             if defer_kv and ecfg.num_blocks is None and ecfg.kv_budget_bytes is None:
                 ecfg.defer_kv = True

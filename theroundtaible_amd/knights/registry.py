@@ -93,7 +93,8 @@ class BackendFactory:
                             kv_cache_fraction=float(st.get("kv_cache_fraction", 0.85)),
                             max_kv_tokens=st.get("max_kv_tokens"),
                             use_graphs=bool(st.get("use_graphs", True)),
-                            model_overrides=overrides, weight_quant=st["weight_quant"])
+                            model_overrides=overrides, weight_quant=st["weight_quant"],
+                            kv_dtype=st["kv_dtype"], kv_scale=st["kv_scale"])
         if ecfg.device == "cpu":
             ecfg.dtype = "fp32" if st.get("dtype") in (None, "bf16") and st.get("cpu_fp32", True) else ecfg.dtype
             ecfg.use_graphs = False

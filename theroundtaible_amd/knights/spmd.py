@@ -88,7 +88,7 @@ def build_spmd_backends(config: RoundtableConfig, cluster: Cluster, ui: UI = NUL
         tp = TPInfo(size=len(ranks), rank=ranks.index(cluster.rank), group=groups.get(tuple(ranks)),
                     load_group=load_groups.get(tuple(ranks)))
         ekey = (st["model"], str(st.get("weights", "random:0")), str(st.get("dtype", "bf16")), tuple(ranks),
-                st["weight_quant"])
+                st["weight_quant"], st["kv_dtype"], repr(st["kv_scale"]) if st["kv_dtype"] != "bf16" else "")
         if ekey not in engines:
             model, overrides = resolve_model(st["model"], str(st.get("weights", "random:0")), st.get("model_overrides"))
             dev = "cpu" if str(st.get("device", "")) == "cpu" else cluster.device
@@ -98,7 +98,8 @@ def build_spmd_backends(config: RoundtableConfig, cluster: Cluster, ui: UI = NUL
                                 kv_cache_fraction=float(st.get("kv_cache_fraction", 0.85)),
                                 max_kv_tokens=st.get("max_kv_tokens"),
                                 use_graphs=bool(st.get("use_graphs", True)) and dev.startswith("cuda"),
-                                model_overrides=overrides, weight_quant=st["weight_quant"])
+                                model_overrides=overrides, weight_quant=st["weight_quant"],
+                                kv_dtype=st["kv_dtype"], kv_scale=st["kv_scale"])
             if not ecfg.device.startswith("cuda"):
                 ecfg.dtype = "fp32"
             with failsafe.stage("engine_load"):

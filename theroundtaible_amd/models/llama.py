@@ -70,13 +70,16 @@ class LlamaModel:
     def kv_heads_local(self) -> int:
         return self.n_kv_heads
 
-    def attention(self, q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, meta: AttnMeta) -> torch.Tensor:
+    def attention(self, q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, meta: AttnMeta,
+                  kv_scales=(1.0, 1.0)) -> torch.Tensor:
+        """``kv_scales``: the layer's (k_scale, v_scale), read only with an fp8 K/V pool (launch constants)."""
+        ks, vs = kv_scales
         if meta.kind == "decode":
             return ops.paged_attention_decode(q, kc, vc, meta.block_tables, meta.ctx_lens, self.scale,
                                               meta.num_splits, meta.workspace, groups=meta.groups,
-                                              planned=meta.planned)
+                                              planned=meta.planned, k_scale=ks, v_scale=vs)
         return ops.prefill_attention(q, kc, vc, meta.block_tables, meta.cu_q, meta.start_pos, self.scale,
-                                     meta.tile_map, split=meta.prefill_split)
+                                     meta.tile_map, split=meta.prefill_split, k_scale=ks, v_scale=vs)
 
     def fused_decode_ok(self, ids: torch.Tensor) -> bool:
         """The fused decode path takes up to 16 rows, up to 32 at tp 1 (serving batches: the skinny
@@ -247,11 +250,12 @@ class LlamaModel:
         sw, SK, ALL = dec["split_ws"], ops.SPLIT_K, ops.SPLIT_K | ops.SPLIT_BALANCE
         for l, lw in enumerate(dec["layers"]):
             # (``*_scale``: fp8 weights' row scales / mxfp4 weights' block scale bytes, absent = bf16)
+            kvs = kv.scales(l)       # (k_scale, v_scale): read only with an fp8 K/V pool
             q = ops.skinny_gemm_rope(res, lw["wqkv"], ops.PRO_NORM, positions, self.cos_sin, kv.k_layer(l),
                                      kv.v_layer(l), meta.slot_mapping, self.n_heads, self.n_kv_heads,
                                      self.head_dim, eps, split_ws=sw, split_mode=SK, bias=lw.get("bqkv"),
-                                     wscale=lw.get("wqkv_scale"))
-            a = self.attention(q, kv.k_layer(l), kv.v_layer(l), meta)
+                                     wscale=lw.get("wqkv_scale"), k_scale=kvs[0], v_scale=kvs[1])
+            a = self.attention(q, kv.k_layer(l), kv.v_layer(l), meta, kvs)
             ops.skinny_gemm(a.reshape(B, -1), lw["wo"], ops.PRO_PLAIN, ops.EPI_RESID, res=res, split_ws=sw,
                             split_mode=SK, wscale=lw.get("wo_scale"))
             g = ops.skinny_gemm(res, lw["w_gate_up"], ops.PRO_NORM, ops.EPI_SWIGLU, eps=eps, split_ws=sw,
@@ -285,8 +289,9 @@ class LlamaModel:
             kc, vc = kv.k_layer(l), kv.v_layer(l)
             q = ops.skinny_gemm_rope(res, lw["wqkv"], ops.PRO_NORM, positions, self.cos_sin, kc, vc,
                                      meta.slot_mapping, self.n_heads, self.n_kv_heads, self.head_dim, eps,
-                                     split_ws=dec["split_ws"], split_mode=0, bias=lw.get("bqkv"))
-            a = self.attention(q, kc, vc, meta)
+                                     split_ws=dec["split_ws"], split_mode=0, bias=lw.get("bqkv"),
+                                     k_scale=kv.scales(l)[0], v_scale=kv.scales(l)[1])
+            a = self.attention(q, kc, vc, meta, kv.scales(l))
             tp.row_parallel(a.reshape(B, -1), lw["wo"], res=res, **sk)
             g = ops.skinny_gemm(res, lw["w_gate_up"], ops.PRO_NORM, ops.EPI_SWIGLU, eps=eps, **sk)
             tp.row_parallel(g, lw["w_down"], res=res, **sk)
@@ -319,9 +324,10 @@ class LlamaModel:
             else:
                 x, res = ops.fused_add_rms_norm(h, res, self._norm_w(l, "attn_norm"), cfg.norm_eps)
             qkv = F.linear(x, self._row_major(l, "wqkv"), lw.get("bqkv"))
+            kvs = kv.scales(l)
             q = ops.rope_and_cache(qkv, positions, self.cos_sin, kv.k_layer(l), kv.v_layer(l), meta.slot_mapping,
-                                   self.n_heads, self.n_kv_heads, self.head_dim)
-            a = self.attention(q, kv.k_layer(l), kv.v_layer(l), meta)
+                                   self.n_heads, self.n_kv_heads, self.head_dim, k_scale=kvs[0], v_scale=kvs[1])
+            a = self.attention(q, kv.k_layer(l), kv.v_layer(l), meta, kvs)
             h = tp.all_reduce(F.linear(a.reshape(T, -1), self._row_major(l, "wo")))
             x, res = ops.fused_add_rms_norm(h, res, self._norm_w(l, "ffn_norm"), cfg.norm_eps)
             g = ops.silu_and_mul(F.linear(x, self._row_major(l, "w_gate_up")))

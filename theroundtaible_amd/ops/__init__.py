@@ -86,13 +86,22 @@ def fused_add_layer_norm(x, residual, w, b, eps):
 
 def rope_and_cache(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: Optional[torch.Tensor],
                    k_cache: torch.Tensor, v_cache: torch.Tensor, slot_mapping: torch.Tensor,
-                   n_heads: int, n_kv_heads: int, head_dim: int) -> torch.Tensor:
+                   n_heads: int, n_kv_heads: int, head_dim: int, k_scale: float = 1.0,
+                   v_scale: float = 1.0) -> torch.Tensor:
+    """``k_scale`` / ``v_scale``: read only with an fp8 cache (uint8 tensors of the same shapes, kv_dtype
+    "fp8"): the cache then takes ``kv_fp8_code(value, 1 / scale)`` bytes (ops/reference.py)."""
     if _use_native(qkv):
         q = torch.empty(qkv.shape[0], n_heads, head_dim, dtype=qkv.dtype, device=qkv.device)
-        native().rope_and_cache(q, qkv, positions, cos_sin if cos_sin is not None else torch.empty(0, device=qkv.device),
-                                k_cache, v_cache, slot_mapping, n_heads, n_kv_heads, head_dim)
+        cs = cos_sin if cos_sin is not None else torch.empty(0, device=qkv.device)
+        if ref.is_fp8_cache(k_cache, v_cache):
+            native().rope_and_cache_fp8(q, qkv, positions, cs, k_cache, v_cache, slot_mapping, n_heads, n_kv_heads,
+                                        head_dim, float(k_scale), float(v_scale))
+        else:
+            native().rope_and_cache(q, qkv, positions, cs, k_cache, v_cache, slot_mapping, n_heads, n_kv_heads,
+                                    head_dim)
         return q
-    return ref.rope_and_cache(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, n_heads, n_kv_heads, head_dim)
+    return ref.rope_and_cache(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, n_heads, n_kv_heads, head_dim,
+                              k_scale, v_scale)
 
 
 # Limits of the decode attention kernels, repeated from csrc/attn_core.h (GROUP_COLS, MAXS, PLAN_HDR)
@@ -210,11 +219,12 @@ def paged_attention_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torc
                            block_tables: torch.Tensor, ctx_lens: torch.Tensor, scale: float,
                            num_splits: int = 1, workspace: Optional[DecodeWorkspace] = None,
                            out: Optional[torch.Tensor] = None, groups: Optional[torch.Tensor] = None,
-                           planned: bool = False) -> torch.Tensor:
+                           planned: bool = False, k_scale: float = 1.0, v_scale: float = 1.0) -> torch.Tensor:
     """``groups`` (optional, device ``[B, 3]`` int32 from :func:`decode_groups`): sequences whose
     block tables share leading blocks decode those keys once for the whole group. The result is
     identical to decoding every sequence alone (the fp32 oracle ignores ``groups``).
-    ``planned``: the workspace holds this step's :func:`attn_plan` for exactly these arguments."""
+    ``planned``: the workspace holds this step's :func:`attn_plan` for exactly these arguments.
+    ``k_scale`` / ``v_scale``: read only with an fp8 cache (uint8, kv_dtype "fp8"; head_dim 128)."""
     if _use_native(q):
         if out is None:
             out = torch.empty_like(q)
@@ -226,13 +236,21 @@ def paged_attention_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torc
             raise ValueError(f"decode workspace too small for shared-prefix groups (max_group "
                              f"{workspace.max_group} < {MAX_GROUP_COLS // G})")
         plan = workspace.plan if planned else None
+        if ref.is_fp8_cache(k_cache, v_cache):
+            native().paged_attention_decode_fp8(out, q, k_cache, v_cache, block_tables, ctx_lens, scale,
+                                                int(num_splits), workspace.partial_o, workspace.partial_ml,
+                                                workspace.counters, groups,
+                                                workspace.slot_stride if groups is not None else 0,
+                                                plan, workspace.plan_stride if planned else 0,
+                                                float(k_scale), float(v_scale))
+            return out
         native().paged_attention_decode(out, q, k_cache, v_cache, block_tables, ctx_lens, scale,
                                         int(num_splits), workspace.partial_o, workspace.partial_ml,
                                         workspace.counters, groups,
                                         workspace.slot_stride if groups is not None else 0, False,
                                         plan, workspace.plan_stride if planned else 0)
         return out
-    return ref.paged_attention_decode(q, k_cache, v_cache, block_tables, ctx_lens, scale)
+    return ref.paged_attention_decode(q, k_cache, v_cache, block_tables, ctx_lens, scale, k_scale, v_scale)
 
 
 def attn_plan(block_tables: torch.Tensor, ctx_lens: torch.Tensor, num_splits: int, workspace: DecodeWorkspace,
@@ -317,12 +335,30 @@ def prefill_split_plan(cu_q: torch.Tensor, rows_per_tile: int, start_pos, n_kv_h
 
 def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_tables: torch.Tensor,
                       cu_q: torch.Tensor, start_pos: torch.Tensor, scale: float,
-                      tile_map: Optional[torch.Tensor] = None, split=None) -> torch.Tensor:
+                      tile_map: Optional[torch.Tensor] = None, split=None, k_scale: float = 1.0,
+                      v_scale: float = 1.0) -> torch.Tensor:
     """``split``: a device-resident :func:`prefill_split_plan` ``(items, cmap, parts)`` — the
-    key-split launch + its combine; ``tile_map`` otherwise (whole tiles)."""
+    key-split launch + its combine; ``tile_map`` otherwise (whole tiles).
+    ``k_scale`` / ``v_scale``: read only with an fp8 cache (uint8, kv_dtype "fp8"), which has the
+    32x32 kernel only: head_dim 128 and a GQA group <= 8, anything else is refused."""
     if _use_native(q):
         nat = native()
         out = torch.empty_like(q)
+        if ref.is_fp8_cache(k_cache, v_cache):
+            hkv, D = k_cache.shape[1], q.shape[2]
+            if split is not None:
+                items, cmap, parts = split
+                part_o = torch.empty(parts * hkv * 8 * 32 * D, dtype=torch.float32, device=q.device)
+                part_ml = torch.empty(parts * hkv * 8 * 32 * 2, dtype=torch.float32, device=q.device)
+                nat.prefill_attention_fp8(out, q, k_cache, v_cache, block_tables, cu_q, start_pos, items, scale,
+                                          float(k_scale), float(v_scale), cmap, part_o, part_ml, int(parts))
+                return out
+            if tile_map is None:
+                rows = nat.prefill_rows_per_tile(q.shape[1] // hkv, D)
+                tile_map = prefill_tile_map(cu_q.cpu(), rows, start_pos.cpu()).to(q.device)
+            nat.prefill_attention_fp8(out, q, k_cache, v_cache, block_tables, cu_q, start_pos, tile_map, scale,
+                                      float(k_scale), float(v_scale))
+            return out
         if split is not None:
             items, cmap, parts = split
             hkv, D = k_cache.shape[1], q.shape[2]
@@ -336,7 +372,8 @@ def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
             tile_map = prefill_tile_map(cu_q.cpu(), rows, start_pos.cpu()).to(q.device)
         nat.prefill_attention(out, q, k_cache, v_cache, block_tables, cu_q, start_pos, tile_map, scale)
         return out
-    return ref.prefill_attention(q, k_cache, v_cache, block_tables, cu_q.cpu(), start_pos.cpu(), scale)
+    return ref.prefill_attention(q, k_cache, v_cache, block_tables, cu_q.cpu(), start_pos.cpu(), scale, k_scale,
+                                 v_scale)
 
 
 PRO_PLAIN, PRO_NORM, PRO_NORM_ADD = 0, 1, 2
@@ -571,7 +608,8 @@ def skinny_gemm_rope(x: torch.Tensor, Ws: torch.Tensor, pro: int, positions: tor
                      n_kv_heads: int, head_dim: int, eps: float = 1e-5, x2: Optional[torch.Tensor] = None,
                      xout: Optional[torch.Tensor] = None, split_ws: Optional[torch.Tensor] = None,
                      split_mode: int = SPLIT_K | SPLIT_BALANCE, bias: Optional[torch.Tensor] = None,
-                     wscale: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     wscale: Optional[torch.Tensor] = None, k_scale: float = 1.0,
+                     v_scale: float = 1.0) -> torch.Tensor:
     """Decode qkv projection (+ optional RMSNorm prologue) with RoPE and the paged K/V cache
     write fused into the epilogue; returns q [M, n_heads, head_dim]. ``Ws`` must come from
     ``shuffle_weight(Wqkv, gamma, rope_heads=n_heads + n_kv_heads, head_dim=head_dim)``.
@@ -579,16 +617,25 @@ def skinny_gemm_rope(x: torch.Tensor, Ws: torch.Tensor, pro: int, positions: tor
     ``bias`` (Qwen2 q/k/v bias, added after the norm scale and before RoPE) must come from
     :func:`rope_bias` (fp32, the shuffled weight's column order).
     ``wscale``: fp8 weights, as in :func:`skinny_gemm` (``Ws`` from ``shuffle_weight_fp8`` with the
-    same ``rope_heads`` / ``head_dim``; uint8 ``wscale``: from ``shuffle_weight_mxfp4``)."""
+    same ``rope_heads`` / ``head_dim``; uint8 ``wscale``: from ``shuffle_weight_mxfp4``).
+    ``k_scale`` / ``v_scale``: read only with an fp8 cache (uint8, kv_dtype "fp8"): the epilogue then
+    stores ``kv_fp8_code`` of its finished fp32 sums (after bias and RoPE), for every weight type."""
+    ks = (float(k_scale), float(v_scale))
     if wscale is not None and wscale.dtype == torch.uint8:
         _mxfp4_check(x, Ws, wscale, pro, x2, xout, split_ws, "skinny_gemm_rope")
         if not _use_native(x):
             return ref.skinny_gemm_rope(x, ref.dequantize_mxfp4(Ws, wscale), pro, positions, cos_sin, k_cache,
-                                        v_cache, slots, n_heads, n_kv_heads, head_dim, eps, None, None, bias)
+                                        v_cache, slots, n_heads, n_kv_heads, head_dim, eps, None, None, bias, *ks)
         M = x.shape[0]
         q = torch.empty(M, n_heads, head_dim, dtype=x.dtype, device=x.device)
+        kv8 = ref.is_fp8_cache(k_cache, v_cache)
         for a in range(0, M, 16):
             b = min(M, a + 16)
+            if kv8:
+                native().skinny_gemm_rope_kv8(q[a:b], x[a:b], Ws, wscale, pro, positions[a:b], cos_sin, k_cache,
+                                              v_cache, slots[a:b], n_heads, n_kv_heads, head_dim, eps, bias=bias,
+                                              k_scale=ks[0], v_scale=ks[1])
+                continue
             native().skinny_gemm_rope_mxfp4(q[a:b], x[a:b], Ws, wscale, pro, positions[a:b], cos_sin, k_cache,
                                             v_cache, slots[a:b], n_heads, n_kv_heads, head_dim, eps, bias)
         return q
@@ -596,11 +643,17 @@ def skinny_gemm_rope(x: torch.Tensor, Ws: torch.Tensor, pro: int, positions: tor
         _fp8_check(x, Ws, wscale, pro, x2, xout, split_ws, "skinny_gemm_rope")
         if not _use_native(x):
             return ref.skinny_gemm_rope(x, ref.dequantize_fp8(Ws, wscale), pro, positions, cos_sin, k_cache,
-                                        v_cache, slots, n_heads, n_kv_heads, head_dim, eps, None, None, bias)
+                                        v_cache, slots, n_heads, n_kv_heads, head_dim, eps, None, None, bias, *ks)
         M = x.shape[0]
         q = torch.empty(M, n_heads, head_dim, dtype=x.dtype, device=x.device)
+        kv8 = ref.is_fp8_cache(k_cache, v_cache)
         for a in range(0, M, 16):
             b = min(M, a + 16)
+            if kv8:
+                native().skinny_gemm_rope_kv8(q[a:b], x[a:b], Ws, wscale, pro, positions[a:b], cos_sin, k_cache,
+                                              v_cache, slots[a:b], n_heads, n_kv_heads, head_dim, eps, bias=bias,
+                                              k_scale=ks[0], v_scale=ks[1])
+                continue
             native().skinny_gemm_rope_fp8(q[a:b], x[a:b], Ws, wscale, pro, positions[a:b], cos_sin, k_cache, v_cache,
                                           slots[a:b], n_heads, n_kv_heads, head_dim, eps, bias)
         return q
@@ -608,11 +661,16 @@ def skinny_gemm_rope(x: torch.Tensor, Ws: torch.Tensor, pro: int, positions: tor
         raise ValueError("skinny_gemm_rope: uint8 (fp8 / mxfp4) weights need their wscale")
     if _use_native(x):
         q = torch.empty(x.shape[0], n_heads, head_dim, dtype=x.dtype, device=x.device)
+        if ref.is_fp8_cache(k_cache, v_cache):
+            native().skinny_gemm_rope_kv8(q, x, Ws, None, pro, positions, cos_sin, k_cache, v_cache, slots, n_heads,
+                                          n_kv_heads, head_dim, eps, x2, xout, split_ws, int(split_mode), bias,
+                                          ks[0], ks[1])
+            return q
         native().skinny_gemm_rope(q, x, Ws, pro, positions, cos_sin, k_cache, v_cache, slots, n_heads, n_kv_heads,
                                   head_dim, eps, x2, xout, split_ws, int(split_mode), bias)
         return q
     return ref.skinny_gemm_rope(x, Ws, pro, positions, cos_sin, k_cache, v_cache, slots, n_heads, n_kv_heads,
-                                head_dim, eps, x2, xout, bias)
+                                head_dim, eps, x2, xout, bias, *ks)
 
 
 def rope_bias(b: torch.Tensor, n_heads: int, n_kv_heads: int, head_dim: int) -> torch.Tensor:

@@ -854,14 +854,56 @@ def attn_table3_case(kind, hq, hkv, d) -> AttnCase:
     return attn_case(kind, hq, hkv, d, [(l - 1, 1) for l in lens], [(label, sh)] * len(lens))
 
 
+def attn_case_fp8(case: AttnCase, k_scale: float = 1.0, v_scale: float = 1.0) -> AttnCase:
+    """The fp8-KV twin of ``case`` (kv_dtype "fp8", ops/reference.py ``kv_fp8_code``): the same q,
+    block tables and lengths; ``k_cache`` / ``v_cache`` hold the e4m3fn codes (uint8) of every slot of
+    the bf16 caches, poison included, under ``k_scale`` / ``v_scale`` in the fp8 block byte order;
+    ``k_deq`` / ``v_deq`` hold ``e4m3(code) * scale`` in fp64 in the bf16 caches' layout, which is
+    what :func:`attn_oracle` of the twin computes from. The convert is exact and the two scale folds
+    of the kernels (k_scale into the softmax scale, v_scale into the final 1/l) are fp32 roundings
+    far inside ATTN_SLACK, so the twin's tolerance is ``attn_tol`` of its own oracle, unchanged.
+    Every code is finite: inputs are finite and the encode saturates at +-448 (V poison 96 / v_scale
+    and the K poison round to finite codes)."""
+    from .reference import k_rows, kv_fp8_code, kv_fp8_inv, kv_fp8_value, write_k, write_k_fp8, write_v_fp8
+    nb, hkv, bs, d = case.k_cache.shape
+    blocks = torch.arange(nb)
+    allb, off = blocks.repeat_interleave(bs), torch.arange(bs).repeat(nb)
+    K = k_rows(case.k_cache, blocks).float()                                     # [nb * bs, hkv, d]
+    V = case.v_cache[blocks].permute(0, 3, 1, 2).reshape(nb * bs, hkv, d).float()
+    kc, vc = kv_fp8_code(K, kv_fp8_inv(k_scale)), kv_fp8_code(V, kv_fp8_inv(v_scale))
+    # A NONZERO value whose code would be +-0 takes the smallest code of its sign (+-2^-9) instead; the
+    # census kinds' exact zeros stay zero. Reason: e4m3 keeps 4 significant bits of K, which turns the
+    # steepest ramp (8 log2 units per key) into plateaus of 16 equal keys 128 log2 units apart. Where a
+    # plateau's only visible key had a zero V code, the exact output would be 2^-128 of the row's
+    # largest weight: below the fp32 normal range relative to it, which neither attn_tol's derivation
+    # (fp32 arithmetic without underflow) nor the kernels' exp2 (results below 2^-126 of the row
+    # maximum are dropped, csrc/common.h fast_exp2) covers. bf16 inputs never have this structure
+    # (their ramps are exact and a random bf16 V is never exactly 0); the twin must not add it.
+    lost = (V != 0) & ((vc & 0x7F) == 0)
+    vc = torch.where(lost, (vc & 0x80) | 1, vc)
+    k8 = torch.zeros(nb, hkv, bs, d, dtype=torch.uint8)
+    v8 = torch.zeros(nb, hkv, d, bs, dtype=torch.uint8)
+    write_k_fp8(k8, allb, off, kc)
+    write_v_fp8(v8, allb, off, vc)
+    kd = torch.empty(nb, hkv, bs, d, dtype=torch.float64)
+    vd = torch.empty(nb, hkv, d, bs, dtype=torch.float64)
+    write_k(kd, allb, off, kv_fp8_value(kc).double() * float(k_scale))
+    vd[allb, :, :, off] = kv_fp8_value(vc).double() * float(v_scale)
+    assert bool(torch.isfinite(kd).all()) and bool(torch.isfinite(vd).all())
+    twin = AttnCase(**case.__dict__)
+    twin.k_cache, twin.v_cache, twin.k_deq, twin.v_deq = k8, v8, kd, vd
+    twin.k_scale, twin.v_scale = float(k_scale), float(v_scale)
+    twin.v_lifted = int(lost.sum())      # V codes that are not kv_fp8_code's own (tests bound the count)
+    return twin
+
+
 def attn_oracle(case: AttnCase, prefill: bool = False):
-    """-> (e, A, tol) of ``case``."""
+    """-> (e, A, tol) of ``case``; an fp8 twin (:func:`attn_case_fp8`) is judged on its dequantised values."""
+    kc, vc = (case.k_deq, case.v_deq) if hasattr(case, "k_deq") else (case.k_cache, case.v_cache)
     if prefill:
-        e, A = prefill_attention64(case.q, case.k_cache, case.v_cache, case.block_tables, case.cu_q, case.start_pos,
-                                   case.scale)
+        e, A = prefill_attention64(case.q, kc, vc, case.block_tables, case.cu_q, case.start_pos, case.scale)
     else:
-        e, A = paged_attention_decode64(case.q, case.k_cache, case.v_cache, case.block_tables, case.ctx_lens,
-                                        case.scale)
+        e, A = paged_attention_decode64(case.q, kc, vc, case.block_tables, case.ctx_lens, case.scale)
     return e, A, attn_tol(e, A, case.p_exact)
 
 

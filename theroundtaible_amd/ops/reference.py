@@ -106,8 +106,10 @@ def _rotate(x: torch.Tensor, cs: torch.Tensor) -> torch.Tensor:
 
 def rope_and_cache(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: Optional[torch.Tensor],
                    k_cache: torch.Tensor, v_cache: torch.Tensor, slot_mapping: torch.Tensor,
-                   n_heads: int, n_kv_heads: int, head_dim: int) -> torch.Tensor:
-    """Split fused qkv, rotate q/k (if cos_sin given), scatter k/v into the paged cache, return q."""
+                   n_heads: int, n_kv_heads: int, head_dim: int, k_scale: float = 1.0,
+                   v_scale: float = 1.0) -> torch.Tensor:
+    """Split fused qkv, rotate q/k (if cos_sin given), scatter k/v into the paged cache, return q.
+    An fp8 cache (uint8, :func:`kv_fp8_code`) takes the codes of the fp32 k / v under the scales."""
     T = qkv.shape[0]
     q = qkv[:, :n_heads * head_dim].reshape(T, n_heads, head_dim).float()
     k = qkv[:, n_heads * head_dim:(n_heads + n_kv_heads) * head_dim].reshape(T, n_kv_heads, head_dim).float()
@@ -119,9 +121,88 @@ def rope_and_cache(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: Optional
     bs = k_cache.shape[2]
     slots = slot_mapping.long()
     blk, off = slots // bs, slots % bs
+    if is_fp8_cache(k_cache, v_cache):
+        write_k_fp8(k_cache, blk, off, kv_fp8_code(k, kv_fp8_inv(k_scale)))
+        write_v_fp8(v_cache, blk, off, kv_fp8_code(v.float(), kv_fp8_inv(v_scale)))
+        return q.to(qkv.dtype)
     write_k(k_cache, blk, off, k)
     v_cache[blk, :, :, off] = v.to(v_cache.dtype)
     return q.to(qkv.dtype)
+
+
+# ---- FP8 K/V cache (kv_dtype "fp8"; csrc/kv_fp8_core.h is the same rule on host and device) ----
+KV_FP8_MAX = 448.0        # largest finite OCP e4m3fn value
+KV_FP8_NAN = 0x7F
+
+
+def kv_fp8_inv(scale: float) -> torch.Tensor:
+    """The fp32 ``1 / scale`` every writer multiplies by (one IEEE fp32 division, as the launchers')."""
+    return torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(scale), dtype=torch.float32)
+
+
+def kv_fp8_code(y: torch.Tensor, inv_scale) -> torch.Tensor:
+    """The cache byte (uint8) of fp32 ``y``: e4m3fn round-to-nearest-even of ``clamp(y * inv_scale,
+    +-448)`` — one fp32 multiply, the clamp BEFORE the cast (torch's cast gives NaN, not 448, above
+    464), +-inf saturates, NaN gives the NaN code 0x7f. The sign bit is kept."""
+    inv = torch.as_tensor(inv_scale, dtype=torch.float32).to(y.device)
+    t = y.float() * inv
+    nan = torch.isnan(t)
+    t = torch.where(nan, torch.zeros_like(t), t).clamp(-KV_FP8_MAX, KV_FP8_MAX)
+    codes = t.to(torch.float8_e4m3fn).view(torch.uint8)
+    return torch.where(nan, torch.full_like(codes, KV_FP8_NAN), codes)
+
+
+def kv_fp8_value(codes: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    """fp32 ``e4m3(code) * scale`` (the convert is exact: every e4m3 value is a bf16 value)."""
+    return codes.view(torch.float8_e4m3fn).float() * torch.tensor(float(scale), dtype=torch.float32).to(codes.device)
+
+
+def is_fp8_cache(k_cache: torch.Tensor, v_cache: Optional[torch.Tensor] = None) -> bool:
+    """Whether the caches are the one-byte caches of kv_dtype "fp8"; mixed K/V dtypes are refused."""
+    if v_cache is not None and v_cache.dtype != k_cache.dtype:
+        raise ValueError(f"mixed K/V cache dtypes: {k_cache.dtype} / {v_cache.dtype}")
+    return k_cache.dtype == torch.uint8
+
+
+def k_blocks_fp8(k_cache: torch.Tensor) -> torch.Tensor:
+    """The byte order of an fp8 K cache ``[NB, Hkv, BS, D]`` (csrc/common.h kc8_elem): 64-dim-chunk
+    major, ``[NB, Hkv, D/64, BS, 64]``."""
+    nb, hkv, bs, d = k_cache.shape
+    return k_cache.view(nb, hkv, d // 64, bs, 64)
+
+
+def v_blocks_fp8(v_cache: torch.Tensor) -> torch.Tensor:
+    """The byte order of an fp8 V cache ``[NB, Hkv, D, BS]`` (csrc/common.h vc8_elem):
+    ``[NB, Hkv, D/32 e, 16 r, BS/8 g, 2 u, 8 j]`` holds dim ``32e + 16u + r`` of key ``8g + j``."""
+    nb, hkv, d, bs = v_cache.shape
+    return v_cache.view(nb, hkv, d // 32, 16, bs // 8, 2, 8)
+
+
+def write_k_fp8(k_cache: torch.Tensor, blk: torch.Tensor, off: torch.Tensor, codes: torch.Tensor) -> None:
+    """Store key code rows ``[T, n_kv_heads, head_dim]`` (uint8) at (block, offset) pairs."""
+    T, hkv, d = codes.shape
+    k_blocks_fp8(k_cache)[blk, :, :, off, :] = codes.reshape(T, hkv, d // 64, 64)
+
+
+def write_v_fp8(v_cache: torch.Tensor, blk: torch.Tensor, off: torch.Tensor, codes: torch.Tensor) -> None:
+    """Store value code rows ``[T, n_kv_heads, head_dim]`` (uint8) at (block, offset) pairs."""
+    T, hkv, d = codes.shape
+    c = codes.reshape(T, hkv, d // 32, 2, 16).permute(0, 1, 2, 4, 3)          # [T, Hkv, e, r, u]
+    v_blocks_fp8(v_cache)[blk, :, :, :, off // 8, :, off % 8] = c
+
+
+def k_rows_fp8(k_cache: torch.Tensor, blocks: torch.Tensor) -> torch.Tensor:
+    """Key code rows of ``blocks`` in order: ``[len(blocks) * block_size, n_kv_heads, head_dim]`` uint8."""
+    kb = k_blocks_fp8(k_cache)[blocks]                   # [n, Hkv, D/64, BS, 64]
+    n, hkv, c, bs, w = kb.shape
+    return kb.permute(0, 3, 1, 2, 4).reshape(n * bs, hkv, c * w)
+
+
+def v_rows_fp8(v_cache: torch.Tensor, blocks: torch.Tensor) -> torch.Tensor:
+    """Value code rows of ``blocks`` in order: ``[len(blocks) * block_size, n_kv_heads, head_dim]`` uint8."""
+    vb = v_blocks_fp8(v_cache)[blocks]                   # [n, Hkv, e, r, g, u, j]
+    n, hkv, e, r, g, u, j = vb.shape
+    return vb.permute(0, 4, 6, 1, 2, 5, 3).reshape(n * g * j, hkv, e * u * r)
 
 
 def k_blocks(k_cache: torch.Tensor) -> torch.Tensor:
@@ -148,24 +229,28 @@ def set_k_row(k_cache: torch.Tensor, blk: int, head: int, off: int, row: torch.T
     k_blocks(k_cache)[blk, head, :, off, :] = row.reshape(-1, 32).to(k_cache.dtype)
 
 
-def _gather_kv(k_cache, v_cache, block_table, n):
+def _gather_kv(k_cache, v_cache, block_table, n, k_scale: float = 1.0, v_scale: float = 1.0):
     bs = k_cache.shape[2]
     nblk = (n + bs - 1) // bs
     blocks = block_table[:nblk].long()
+    if is_fp8_cache(k_cache, v_cache):
+        return (kv_fp8_value(k_rows_fp8(k_cache, blocks)[:n], k_scale),
+                kv_fp8_value(v_rows_fp8(v_cache, blocks)[:n], v_scale))
     k = k_rows(k_cache, blocks)[:n]
     v = v_cache[blocks].permute(0, 3, 1, 2).reshape(nblk * bs, v_cache.shape[1], -1)[:n]
     return k.float(), v.float()
 
 
 def paged_attention_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
-                           block_tables: torch.Tensor, ctx_lens: torch.Tensor, scale: float) -> torch.Tensor:
+                           block_tables: torch.Tensor, ctx_lens: torch.Tensor, scale: float,
+                           k_scale: float = 1.0, v_scale: float = 1.0) -> torch.Tensor:
     B, Hq, D = q.shape
     Hkv = k_cache.shape[1]
     G = Hq // Hkv
     out = torch.empty_like(q)
     for b in range(B):
         n = int(ctx_lens[b])
-        k, v = _gather_kv(k_cache, v_cache, block_tables[b], n)     # [n, Hkv, D]
+        k, v = _gather_kv(k_cache, v_cache, block_tables[b], n, k_scale, v_scale)     # [n, Hkv, D]
         qb = q[b].float().reshape(Hkv, G, D)
         s = torch.einsum("hgd,nhd->hgn", qb, k) * scale
         p = torch.softmax(s, dim=-1)
@@ -176,7 +261,7 @@ def paged_attention_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torc
 
 def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                       block_tables: torch.Tensor, cu_q: torch.Tensor, start_pos: torch.Tensor,
-                      scale: float) -> torch.Tensor:
+                      scale: float, k_scale: float = 1.0, v_scale: float = 1.0) -> torch.Tensor:
     """Varlen causal attention: sequence s has queries cu_q[s]:cu_q[s+1] at absolute positions
     start_pos[s] + i, attending to cached keys [0, start_pos[s] + i]."""
     T, Hq, D = q.shape
@@ -189,7 +274,7 @@ def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
             continue
         st = int(start_pos[s])
         n = st + (b - a)
-        k, v = _gather_kv(k_cache, v_cache, block_tables[s], n)
+        k, v = _gather_kv(k_cache, v_cache, block_tables[s], n, k_scale, v_scale)
         qs = q[a:b].float().reshape(b - a, Hkv, G, D)
         sc = torch.einsum("thgd,nhd->thgn", qs, k) * scale
         qpos = torch.arange(st, n)[:, None]
@@ -344,7 +429,7 @@ def skinny_gemm(x, Wf, pro=0, epi=0, res=None, eps=1e-5, x2=None, xout=None):
 
 
 def skinny_gemm_rope(x, Wp, pro, positions, cos_sin, k_cache, v_cache, slots, n_heads, n_kv_heads, head_dim,
-                     eps=1e-5, x2=None, xout=None, bias=None):
+                     eps=1e-5, x2=None, xout=None, bias=None, k_scale: float = 1.0, v_scale: float = 1.0):
     """ROPE-epilogue semantics: fp32 projection on the pair-permuted weight (+ the fp32 bias in
     the same column order, :func:`rope_bias`), columns restored to natural order, then RoPE +
     paged K/V scatter with no bf16 rounding in between."""
@@ -354,7 +439,8 @@ def skinny_gemm_rope(x, Wp, pro, positions, cos_sin, k_cache, v_cache, slots, n_
     perm = rope_row_perm(Wp.shape[0], n_heads + n_kv_heads, head_dim)
     qkv = torch.empty_like(y)
     qkv[:, perm] = y
-    q = rope_and_cache(qkv, positions, cos_sin, k_cache, v_cache, slots, n_heads, n_kv_heads, head_dim)
+    q = rope_and_cache(qkv, positions, cos_sin, k_cache, v_cache, slots, n_heads, n_kv_heads, head_dim, k_scale,
+                       v_scale)
     return q.to(x.dtype)
 
 

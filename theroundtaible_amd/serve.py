@@ -978,7 +978,7 @@ def build_server(model: str, weights: str = "random:0", device: str = "cuda:0", 
                  host: str = "127.0.0.1", port: int = 8000, max_batch: int = 16, max_tokens: int = 512,
                  use_graphs: bool = True, num_blocks: Optional[int] = None,
                  tp: int = 1, op_limit_s: float = 660.0,
-                 weight_quant: Optional[str] = None) -> Optional[RoundtableServer]:
+                 weight_quant: Optional[str] = None, kv_dtype: Optional[str] = None) -> Optional[RoundtableServer]:
     """The server (rank 0), or — on a follower rank of a ``tp > 1`` launch — None after that
     rank has served rank 0's operations until shutdown."""
     # a checkpoint directory defines the architecture: preset + shape overrides from config.json
@@ -1006,7 +1006,7 @@ def build_server(model: str, weights: str = "random:0", device: str = "cuda:0", 
             device = cluster.device
     ecfg = EngineConfig(model=model, weights=weights, device=device, dtype=dtype, use_graphs=use_graphs,
                         max_batch=max_batch, num_blocks=num_blocks, model_overrides=overrides,
-                        weight_quant=weight_quant)
+                        weight_quant=weight_quant, kv_dtype=kv_dtype)
     if ecfg.device == "cpu":
         ecfg.dtype = "fp32" if dtype == "bf16" else dtype
         ecfg.use_graphs = False
