@@ -129,6 +129,11 @@ int launch_skinny_gemm_rope_fp4(void* q_out, const void* x, const void* Wq, cons
                                 int pro, float eps, const int64_t* positions, const float* cos_sin, void* k_cache,
                                 void* v_cache, const int64_t* slots, int Hq, int Hkv, int D, int BS,
                                 const float* bias, hipStream_t stream);
+// QK-norm (Qwen3) + RoPE + paged K/V write, bf16 or fp8 cache: qk_norm_rope.hip
+int launch_qk_norm_rope(void* q_out, const void* qkv, const int64_t* positions, const float* cos_sin,
+                        const void* q_gamma, const void* k_gamma, float eps, void* k_cache, void* v_cache,
+                        const int64_t* slots, int T, int Hq, int Hkv, int D, int BS, int64_t qkv_stride, bool rope,
+                        bool kv8, float k_scale, float v_scale, hipStream_t stream);
 // fp8 K/V cache (kv_dtype "fp8"): rope_cache.hip, attention_decode.hip, attention_prefill.hip, gemm_skinny.hip
 int launch_rope_cache_fp8(void* q_out, const void* qkv, const int64_t* positions, const float* cos_sin,
                           void* k_cache, void* v_cache, const int64_t* slots, int T, int Hq, int Hkv, int D, int BS,
@@ -1159,6 +1164,66 @@ void rope_and_cache_fp8(torch::Tensor q_out, torch::Tensor qkv, torch::Tensor po
   TORCH_CHECK(rc == 0, "rope_and_cache (fp8 KV): unsupported configuration (rc=", rc, ")");
 }
 
+// K2n: per-head QK-norm + RoPE + paged K/V write (csrc/qk_norm_rope.hip). The checks of rope_and_cache /
+// rope_and_cache_fp8 plus the two [D] bf16 gammas; the plan (qk_norm_plan.h) refuses the rest before a launch.
+void qk_norm_rope_common(torch::Tensor& q_out, torch::Tensor& qkv, torch::Tensor& q_gamma, torch::Tensor& k_gamma,
+                         double eps, torch::Tensor& positions, torch::Tensor& cos_sin, torch::Tensor& k_cache,
+                         torch::Tensor& v_cache, torch::Tensor& slots, int64_t Hq, int64_t Hkv, int64_t D, bool fp8,
+                         double k_scale, double v_scale) {
+  const char* who = fp8 ? "qk_norm_rope_and_cache (fp8 KV)" : "qk_norm_rope_and_cache";
+  check_bf16(q_out, "q_out");
+  TORCH_CHECK(qkv.is_cuda() && qkv.dim() == 2 && qkv.scalar_type() == torch::kBFloat16 && qkv.stride(-1) == 1,
+              "qkv must be bf16 rows");
+  check_type(positions, torch::kInt64, "positions");
+  check_type(slots, torch::kInt64, "slot_mapping");
+  check_caches(k_cache, v_cache, Hkv, D, fp8);
+  if (fp8) check_kv_scales(k_scale, v_scale, who);
+  check_bf16(q_gamma, "q_gamma");
+  check_bf16(k_gamma, "k_gamma");
+  TORCH_CHECK(q_gamma.dim() == 1 && k_gamma.dim() == 1 && q_gamma.numel() == D && k_gamma.numel() == D, who,
+              ": q_gamma / k_gamma must be [head_dim] = [", D, "] (got ", q_gamma.numel(), ", ", k_gamma.numel(), ")");
+  TORCH_CHECK(q_gamma.device() == qkv.device() && k_gamma.device() == qkv.device() && q_out.device() == qkv.device() &&
+                  k_cache.device() == qkv.device() && positions.device() == qkv.device() &&
+                  slots.device() == qkv.device(), who, ": operands on different devices");
+  const int64_t T = qkv.size(0);
+  TORCH_CHECK(Hq >= 1 && Hkv >= 1, who, ": head counts must be positive");
+  TORCH_CHECK(qkv.size(1) == (Hq + 2 * Hkv) * D, "qkv width mismatch");
+  TORCH_CHECK(T == 0 || qkv.stride(0) >= qkv.size(1), who, ": qkv rows overlap");
+  TORCH_CHECK(positions.numel() == T && slots.numel() == T && q_out.numel() == T * Hq * D, "token count mismatch");
+  TORCH_CHECK(D == 64 || D == 128, who, ": head_dim must be 64 or 128 (one wave per head, lane l holds dims l and l + D/2)");
+  TORCH_CHECK(!fp8 || k_cache.size(2) % 8 == 0,
+              "fp8 KV: block_size must be a multiple of 8 (block layouts [D/64][BS][64], [D/32][16][BS/8][2][8])");
+  TORCH_CHECK(std::isfinite(eps) && eps >= 0 && std::isfinite((float)eps), who, ": eps must be finite and >= 0 (got ", eps,
+              ")");
+  const bool rope = cos_sin.numel() > 0;
+  if (rope) {
+    check_type(cos_sin, torch::kFloat32, "cos_sin");
+    TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == D && cos_sin.device() == qkv.device(),
+                "cos_sin must be [max_pos, D]");
+  }
+  const int rc = launch_qk_norm_rope(q_out.data_ptr(), qkv.data_ptr(), positions.data_ptr<int64_t>(),
+                                     rope ? cos_sin.data_ptr<float>() : nullptr, q_gamma.data_ptr(), k_gamma.data_ptr(),
+                                     (float)eps, k_cache.data_ptr(), v_cache.data_ptr(), slots.data_ptr<int64_t>(),
+                                     (int)T, (int)Hq, (int)Hkv, (int)D, (int)k_cache.size(2), qkv.stride(0), rope, fp8,
+                                     fp8 ? (float)k_scale : 1.f, fp8 ? (float)v_scale : 1.f, cur_stream());
+  TORCH_CHECK(rc == 0, who, ": unsupported configuration (rc=", rc, ")");
+}
+
+void qk_norm_rope_and_cache(torch::Tensor q_out, torch::Tensor qkv, torch::Tensor q_gamma, torch::Tensor k_gamma,
+                            double eps, torch::Tensor positions, torch::Tensor cos_sin, torch::Tensor k_cache,
+                            torch::Tensor v_cache, torch::Tensor slots, int64_t Hq, int64_t Hkv, int64_t D) {
+  qk_norm_rope_common(q_out, qkv, q_gamma, k_gamma, eps, positions, cos_sin, k_cache, v_cache, slots, Hq, Hkv, D, false,
+                      1.0, 1.0);
+}
+
+void qk_norm_rope_and_cache_fp8(torch::Tensor q_out, torch::Tensor qkv, torch::Tensor q_gamma, torch::Tensor k_gamma,
+                                double eps, torch::Tensor positions, torch::Tensor cos_sin, torch::Tensor k_cache,
+                                torch::Tensor v_cache, torch::Tensor slots, int64_t Hq, int64_t Hkv, int64_t D,
+                                double k_scale, double v_scale) {
+  qk_norm_rope_common(q_out, qkv, q_gamma, k_gamma, eps, positions, cos_sin, k_cache, v_cache, slots, Hq, Hkv, D, true,
+                      k_scale, v_scale);
+}
+
 void paged_attention_decode_fp8(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
                                 torch::Tensor block_tables, torch::Tensor ctx_lens, double scale, int64_t num_splits,
                                 torch::Tensor part_o, torch::Tensor part_ml, torch::Tensor counters,
@@ -1306,6 +1371,14 @@ void skinny_gemm_rope_kv8(torch::Tensor q_out, torch::Tensor x, torch::Tensor W,
 }  // namespace
 
 PYBIND11_MODULE(_C, m) {
+  m.def("qk_norm_rope_and_cache", &qk_norm_rope_and_cache, "K2n: per-head QK-norm + RoPE + paged K/V write",
+        py::arg("q_out"), py::arg("qkv"), py::arg("q_gamma"), py::arg("k_gamma"), py::arg("eps"), py::arg("positions"),
+        py::arg("cos_sin"), py::arg("k_cache"), py::arg("v_cache"), py::arg("slots"), py::arg("Hq"), py::arg("Hkv"),
+        py::arg("D"));
+  m.def("qk_norm_rope_and_cache_fp8", &qk_norm_rope_and_cache_fp8, "K2n with an fp8 (e4m3fn) K/V cache",
+        py::arg("q_out"), py::arg("qkv"), py::arg("q_gamma"), py::arg("k_gamma"), py::arg("eps"), py::arg("positions"),
+        py::arg("cos_sin"), py::arg("k_cache"), py::arg("v_cache"), py::arg("slots"), py::arg("Hq"), py::arg("Hkv"),
+        py::arg("D"), py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0);
   m.def("rope_and_cache_fp8", &rope_and_cache_fp8, "K2 with an fp8 (e4m3fn) K/V cache", py::arg("q_out"),
         py::arg("qkv"), py::arg("positions"), py::arg("cos_sin"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("slots"), py::arg("Hq"), py::arg("Hkv"), py::arg("D"), py::arg("k_scale") = 1.0,

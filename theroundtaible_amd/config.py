@@ -234,6 +234,13 @@ _MODEL_ALIASES = {
     "llama3-8b": ("llama-3-8b", "llama3-8b", "llama-3.1-8b", "meta-llama-3-8b"),
     "llama3-70b": ("llama-3-70b", "llama3-70b", "llama-3.1-70b", "meta-llama-3-70b"),
     "mistral-7b": ("mistral-7b", "mistral-7b-instruct"),
+    # (substring match: "qwen3-14b" does not contain "qwen3-4b", nor does any other pair here overlap)
+    "qwen3-0.6b": ("qwen3-0.6b", "qwen-3-0.6b"),
+    "qwen3-1.7b": ("qwen3-1.7b", "qwen-3-1.7b"),
+    "qwen3-4b": ("qwen3-4b", "qwen-3-4b"),
+    "qwen3-8b": ("qwen3-8b", "qwen-3-8b"),
+    "qwen3-14b": ("qwen3-14b", "qwen-3-14b"),
+    "qwen3-32b": ("qwen3-32b", "qwen-3-32b"),
     "gpt2-small": ("gpt2", "gpt-2", "gpt2-small"),
     "tiny-llama": ("tiny-llama", "tiny"),
 }

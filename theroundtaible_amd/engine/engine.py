@@ -86,7 +86,7 @@ class EngineConfig:
     weight_quant: str = field(default_factory=lambda: resolve_weight_quant(None))
     # K/V page dtype: "bf16" | "fp8" (opt-in). "fp8": OCP e4m3fn codes, one byte per element, value =
     # e4m3(code) * scale with one fp32 k_scale and v_scale per layer (``kv_scale``): the pool holds
-    # twice the tokens and decode attention streams half the bytes. tp 1, Llama / Mistral / Qwen2,
+    # twice the tokens and decode attention streams half the bytes. tp 1, Llama / Mistral / Qwen2 / Qwen3,
     # head_dim 128, GQA group <= 8, bf16 activations on the GPU. Default: "bf16", or
     # ROUNDTABLE_KV_DTYPE when the caller states nothing.
     kv_dtype: str = field(default_factory=lambda: resolve_kv_dtype(None))
@@ -150,7 +150,7 @@ class Engine:
                 raise ConfigError(f"{who} does not support tensor parallel (tp={self.tp.size})",
                                   hint="Run the knight at tp 1 or drop kv_dtype.")
             if self.cfg.arch == "gpt2":
-                raise ConfigError(f"{who} needs a Llama / Mistral / Qwen2 model, not {self.cfg.arch}")
+                raise ConfigError(f"{who} needs a Llama / Mistral / Qwen2 / Qwen3 model, not {self.cfg.arch}")
             if self.on_gpu and self.dtype != torch.bfloat16:
                 raise ConfigError(f"{who} needs dtype bf16 on the GPU (got {ecfg.dtype})")
             G = self.cfg.n_heads // max(1, self.cfg.n_kv_heads)
@@ -170,7 +170,7 @@ class Engine:
             if wq != "none":
                 if not hasattr(self.model, "decode_weights"):
                     raise ConfigError(f"{ecfg.model}: weight_quant={wq!r} needs a model family with fused decode "
-                                      f"weights (Llama / Mistral / Qwen2), not {self.cfg.arch}")
+                                      f"weights (Llama / Mistral / Qwen2 / Qwen3), not {self.cfg.arch}")
                 err = self.model.quant_width_error(wq)
                 if err:
                     raise ConfigError(f"{ecfg.model}: weight_quant={wq!r}: {err}")

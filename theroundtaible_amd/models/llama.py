@@ -1,10 +1,12 @@
-"""Llama-3 / Mistral / Qwen2 decoder (dense, GQA, RoPE, SwiGLU, RMSNorm; Qwen2: q/k/v bias), TP-aware.
+"""Llama-3 / Mistral / Qwen2 / Qwen3 decoder (dense, GQA, RoPE, SwiGLU, RMSNorm; Qwen2: q/k/v bias;
+Qwen3: a per-head RMSNorm of q and k before RoPE, ``cfg.qk_norm``), TP-aware.
 
 Per layer (decode and prefill share the code; only the attention op differs):
 
     x, res = fused_add_rms_norm(h, res)          K1 (HIP)
     qkv    = x @ Wqkv^T                          hipBLASLt (column-parallel)
     q      = rope_and_cache(qkv, ...)            K2 (HIP): RoPE on q/k + paged K/V scatter
+             (Qwen3: qk_norm_rope_and_cache      K2n (HIP): per-head q/k RMSNorm first)
     a      = paged_decode | prefill attention    K3 / K4 (HIP, MFMA)
     h      = a @ Wo^T ; all_reduce               hipBLASLt (row-parallel) + RCCL (C2)
     x, res = fused_add_rms_norm(h, res)          K1
@@ -132,8 +134,10 @@ class LlamaModel:
         return self.quant_width_error("fp8")
 
     # (name, folded norm, shuffle kwargs) of the linears the fused decode path streams
+    # (QK-norm: the qkv GEMM stores plain columns for K2n, so wqkv is not pair-interleaved)
     def _lin_specs(self):
-        return (("wqkv", "attn_norm", {"rope_heads": self.n_heads + self.n_kv_heads, "head_dim": self.head_dim}),
+        qkv_kw = {} if self.cfg.qk_norm else {"rope_heads": self.n_heads + self.n_kv_heads, "head_dim": self.head_dim}
+        return (("wqkv", "attn_norm", qkv_kw),
                 ("wo", None, {}), ("w_gate_up", "ffn_norm", {"swiglu": True}), ("w_down", None, {}))
 
     def decode_weights(self, drop_originals: bool = False, quant: Optional[str] = None):
@@ -178,6 +182,8 @@ class LlamaModel:
                             self.w[f"layers.{i}.{name}"] = None
                     if lw.get("bqkv") is not None:   # Qwen2: the bias the qkv epilogue adds before RoPE
                         d["bqkv"] = ops.rope_bias(lw["bqkv"], self.n_heads, self.n_kv_heads, self.head_dim)
+                    if self.cfg.qk_norm:             # Qwen3: the two [head_dim] gammas K2n reads, as they are
+                        d["q_norm"], d["k_norm"] = lw["q_norm"], lw["k_norm"]
                     layers.append(d)
                 top = {}
                 shuffle(self.w["lm_head"], self.w["final_norm"], top, "lm_head")
@@ -232,6 +238,21 @@ class LlamaModel:
             return ones
         return w
 
+    def _qkv_fused(self, res, lw, positions, kv, l, meta, eps, **gemm_kw):
+        """The fused decode paths' qkv step -> q [B, n_heads, head_dim], K/V written. One launch (the
+        GEMM's RoPE / cache epilogue), or with ``cfg.qk_norm`` two: the GEMM stores the plain
+        [B, (Hq + 2 Hkv) D] row (EPI_STORE: a workgroup owns 16 of a head's columns, so the per-head sum of
+        squares is not available in its epilogue) and K2n normalises, rotates and writes the cache."""
+        kc, vc = kv.k_layer(l), kv.v_layer(l)
+        ks, vs = kv.scales(l)
+        if not self.cfg.qk_norm:
+            return ops.skinny_gemm_rope(res, lw["wqkv"], ops.PRO_NORM, positions, self.cos_sin, kc, vc,
+                                        meta.slot_mapping, self.n_heads, self.n_kv_heads, self.head_dim, eps,
+                                        bias=lw.get("bqkv"), k_scale=ks, v_scale=vs, **gemm_kw)
+        qkv = ops.skinny_gemm(res, lw["wqkv"], ops.PRO_NORM, ops.EPI_STORE, eps=eps, **gemm_kw)
+        return ops.qk_norm_rope_and_cache(qkv, lw["q_norm"], lw["k_norm"], eps, positions, self.cos_sin, kc, vc,
+                                          meta.slot_mapping, self.n_heads, self.n_kv_heads, self.head_dim, ks, vs)
+
     accepts_hidden = True  # forward(..., hidden=) takes pre-gathered embedding rows (decode_prep)
 
     def forward_decode_fused(self, ids: torch.Tensor, positions: torch.Tensor, kv, meta: AttnMeta,
@@ -240,7 +261,9 @@ class LlamaModel:
         (csrc/gemm_skinny.hip): per layer qkv(+RMSNorm, +RoPE/KV-cache write) -> K3 (+ its split
         combine launch) -> o(+residual) -> gate_up(+RMSNorm, SwiGLU) -> down(+residual); no norm /
         rope / reduce kernels. (Folding the combine into the o launch measured slower:
-        tools/experiments/combine_o.hip.)"""
+        tools/experiments/combine_o.hip.) With ``cfg.qk_norm`` (Qwen3) the qkv step is two launches,
+        qkv(+RMSNorm) storing the plain row and K2n (per-head norm + RoPE + cache write): seven
+        launches per layer instead of six (:meth:`_qkv_fused`)."""
         cfg = self.cfg
         eps = cfg.norm_eps
         dec = self.decode_weights()
@@ -251,10 +274,8 @@ class LlamaModel:
         for l, lw in enumerate(dec["layers"]):
             # (``*_scale``: fp8 weights' row scales / mxfp4 weights' block scale bytes, absent = bf16)
             kvs = kv.scales(l)       # (k_scale, v_scale): read only with an fp8 K/V pool
-            q = ops.skinny_gemm_rope(res, lw["wqkv"], ops.PRO_NORM, positions, self.cos_sin, kv.k_layer(l),
-                                     kv.v_layer(l), meta.slot_mapping, self.n_heads, self.n_kv_heads,
-                                     self.head_dim, eps, split_ws=sw, split_mode=SK, bias=lw.get("bqkv"),
-                                     wscale=lw.get("wqkv_scale"), k_scale=kvs[0], v_scale=kvs[1])
+            q = self._qkv_fused(res, lw, positions, kv, l, meta, eps, split_ws=sw, split_mode=SK,
+                                wscale=lw.get("wqkv_scale"))
             a = self.attention(q, kv.k_layer(l), kv.v_layer(l), meta, kvs)
             ops.skinny_gemm(a.reshape(B, -1), lw["wo"], ops.PRO_PLAIN, ops.EPI_RESID, res=res, split_ws=sw,
                             split_mode=SK, wscale=lw.get("wo_scale"))
@@ -277,7 +298,8 @@ class LlamaModel:
         + all-gather (C3). Round 3 instead handed the partial to the next GEMM's NORM_ADD
         prologue, which re-added it in every workgroup: 1-3 us per GEMM at shard shapes
         (profiles/r04/gemm_variants.md). qkv never takes split-K (its seam cost more than the
-        48-192 unsplit tiles lose; same table)."""
+        48-192 unsplit tiles lose; same table). ``cfg.qk_norm``: qkv is two launches, as at tp 1 (seven
+        per layer)."""
         cfg, tp = self.cfg, self.tp
         eps = cfg.norm_eps
         dec = self.decode_weights()
@@ -287,10 +309,7 @@ class LlamaModel:
         sk = dict(split_ws=dec["split_ws"], split_mode=ops.SPLIT_K)
         for l, lw in enumerate(dec["layers"]):
             kc, vc = kv.k_layer(l), kv.v_layer(l)
-            q = ops.skinny_gemm_rope(res, lw["wqkv"], ops.PRO_NORM, positions, self.cos_sin, kc, vc,
-                                     meta.slot_mapping, self.n_heads, self.n_kv_heads, self.head_dim, eps,
-                                     split_ws=dec["split_ws"], split_mode=0, bias=lw.get("bqkv"),
-                                     k_scale=kv.scales(l)[0], v_scale=kv.scales(l)[1])
+            q = self._qkv_fused(res, lw, positions, kv, l, meta, eps, split_ws=dec["split_ws"], split_mode=0)
             a = self.attention(q, kc, vc, meta, kv.scales(l))
             tp.row_parallel(a.reshape(B, -1), lw["wo"], res=res, **sk)
             g = ops.skinny_gemm(res, lw["w_gate_up"], ops.PRO_NORM, ops.EPI_SWIGLU, eps=eps, **sk)
@@ -325,8 +344,13 @@ class LlamaModel:
                 x, res = ops.fused_add_rms_norm(h, res, self._norm_w(l, "attn_norm"), cfg.norm_eps)
             qkv = F.linear(x, self._row_major(l, "wqkv"), lw.get("bqkv"))
             kvs = kv.scales(l)
-            q = ops.rope_and_cache(qkv, positions, self.cos_sin, kv.k_layer(l), kv.v_layer(l), meta.slot_mapping,
-                                   self.n_heads, self.n_kv_heads, self.head_dim, k_scale=kvs[0], v_scale=kvs[1])
+            if cfg.qk_norm:
+                q = ops.qk_norm_rope_and_cache(qkv, lw["q_norm"], lw["k_norm"], cfg.norm_eps, positions, self.cos_sin,
+                                               kv.k_layer(l), kv.v_layer(l), meta.slot_mapping, self.n_heads,
+                                               self.n_kv_heads, self.head_dim, k_scale=kvs[0], v_scale=kvs[1])
+            else:
+                q = ops.rope_and_cache(qkv, positions, self.cos_sin, kv.k_layer(l), kv.v_layer(l), meta.slot_mapping,
+                                       self.n_heads, self.n_kv_heads, self.head_dim, k_scale=kvs[0], v_scale=kvs[1])
             a = self.attention(q, kv.k_layer(l), kv.v_layer(l), meta, kvs)
             h = tp.all_reduce(F.linear(a.reshape(T, -1), self._row_major(l, "wo")))
             x, res = ops.fused_add_rms_norm(h, res, self._norm_w(l, "ffn_norm"), cfg.norm_eps)

@@ -7,7 +7,7 @@ first and then shards them, so TP=1 and TP=N see identical math (TP equivalence
 tests). ``random-dev:<seed>`` does the same with the full tensors generated on the target
 device, one tensor at a time (GPU TP checks at 8B / 70B shapes, where CPU generation of the
 unsharded model would take minutes and tens of GB of host memory per rank).
-A path loads HF-named safetensors (Llama/Mistral/Qwen2/GPT-2 naming) and shards it.
+A path loads HF-named safetensors (Llama/Mistral/Qwen2/Qwen3/GPT-2 naming) and shards it.
 """
 from __future__ import annotations
 
@@ -41,6 +41,9 @@ def llama_layout(cfg: ModelConfig) -> Dict[str, Tuple[Tuple[int, ...], str, Opti
         lay[p + "wqkv"] = (((cfg.n_heads + 2 * cfg.n_kv_heads) * D, H), "normal", "qkv")
         if cfg.qkv_bias:
             lay[p + "bqkv"] = (((cfg.n_heads + 2 * cfg.n_kv_heads) * D,), "normal", "qkv")
+        if cfg.qk_norm:   # Qwen3: one gamma per layer for all q heads, one for all k heads (replicated under tp)
+            lay[p + "q_norm"] = ((D,), "ones", None)
+            lay[p + "k_norm"] = ((D,), "ones", None)
         lay[p + "wo"] = ((H, cfg.n_heads * D), "normal", "col")
         lay[p + "ffn_norm"] = ((H,), "ones", None)
         lay[p + "w_gate_up"] = ((2 * cfg.ffn, H), "normal", "gateup")
@@ -176,6 +179,9 @@ def _hf_llama_name_map(cfg: ModelConfig) -> Dict[str, Callable[[Dict[str, torch.
             m[f"layers.{i}.bqkv"] = lambda t, p=p: torch.cat([t[p + "self_attn.q_proj.bias"],
                                                                t[p + "self_attn.k_proj.bias"],
                                                                t[p + "self_attn.v_proj.bias"]])
+        if cfg.qk_norm:
+            m[f"layers.{i}.q_norm"] = lambda t, p=p: t[p + "self_attn.q_norm.weight"]
+            m[f"layers.{i}.k_norm"] = lambda t, p=p: t[p + "self_attn.k_norm.weight"]
         m[f"layers.{i}.wo"] = lambda t, p=p: t[p + "self_attn.o_proj.weight"]
         m[f"layers.{i}.w_gate_up"] = lambda t, p=p: torch.cat([t[p + "mlp.gate_proj.weight"],
                                                                t[p + "mlp.up_proj.weight"]])

@@ -104,6 +104,28 @@ def rope_and_cache(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: Optional
                               k_scale, v_scale)
 
 
+def qk_norm_rope_and_cache(qkv: torch.Tensor, q_gamma: torch.Tensor, k_gamma: torch.Tensor, eps: float,
+                           positions: torch.Tensor, cos_sin: Optional[torch.Tensor], k_cache: torch.Tensor,
+                           v_cache: torch.Tensor, slot_mapping: torch.Tensor, n_heads: int, n_kv_heads: int,
+                           head_dim: int, k_scale: float = 1.0, v_scale: float = 1.0) -> torch.Tensor:
+    """:func:`rope_and_cache` with Qwen3's per-head RMSNorm of q and k (``q_gamma`` / ``k_gamma``
+    ``[head_dim]``, ``eps``) before the rotation: csrc/qk_norm_rope.hip, one wave per (token, head);
+    ``head_dim`` 64 or 128. ``qkv`` may be a column slice of wider rows; it is only read."""
+    if _use_native(qkv):
+        q = torch.empty(qkv.shape[0], n_heads, head_dim, dtype=qkv.dtype, device=qkv.device)
+        cs = cos_sin if cos_sin is not None else torch.empty(0, device=qkv.device)
+        if ref.is_fp8_cache(k_cache, v_cache):
+            native().qk_norm_rope_and_cache_fp8(q, qkv, q_gamma, k_gamma, float(eps), positions, cs, k_cache, v_cache,
+                                                slot_mapping, n_heads, n_kv_heads, head_dim, float(k_scale),
+                                                float(v_scale))
+        else:
+            native().qk_norm_rope_and_cache(q, qkv, q_gamma, k_gamma, float(eps), positions, cs, k_cache, v_cache,
+                                            slot_mapping, n_heads, n_kv_heads, head_dim)
+        return q
+    return ref.qk_norm_rope_and_cache(qkv, q_gamma, k_gamma, eps, positions, cos_sin, k_cache, v_cache, slot_mapping,
+                                      n_heads, n_kv_heads, head_dim, k_scale, v_scale)
+
+
 # Limits of the decode attention kernels, repeated from csrc/attn_core.h (GROUP_COLS, MAXS, PLAN_HDR)
 # because the CPU path imports without the native module, which exports them as ATTN_GROUP_COLS,
 # ATTN_MAX_SPLITS and ATTN_PLAN_HDR (tests/test_kernels_gpu.py holds the two together).

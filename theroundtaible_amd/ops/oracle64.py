@@ -185,6 +185,69 @@ def rope_tol(e, mag):
     return bf16_ulp(e) + ROPE_SLACK * mag
 
 
+# ---- per-head QK-norm + RoPE (csrc/qk_norm_rope.hip) --------------------------------------------------
+# Tolerance of one output element: qk_norm_tol(e, mag) = bf16_ulp(e) + QKNORM_SLACK * mag, with ``mag`` =
+# :func:`rope`'s magnitude of the NORMALISED values (|y1 c| + |y2 s|; |y| without a rotation). The bf16
+# ulp is the one rounding of the store. The rest (the fp32 sum of squares, rsqrt, two multiplies, the
+# rotation) is QKNORM_SLACK, measured like LOGPROB_SLACK and ATTN_SLACK: the worst |o32 - e| / mag of the
+# fp32 CPU REFERENCE (ops/reference.py qk_norm_rope_and_cache on fp32 copies of the bf16 inputs, so its
+# output carries no bf16 rounding) over every input of QKNORM_SHAPES x QKNORM_T x QKNORM_EPS x {rope,
+# no rope} (QKNORM_REF_WORST; tests/test_qk_norm_cpu.py recomputes and prints it), times 4 for the
+# device's rsqrt, its butterfly summation order and its fused multiply-adds, rounded up to a power of
+# two. It is not tuned against the kernel.
+QKNORM_REF_WORST = 3.04e-7       # measured (tests/test_qk_norm_cpu.py::test_reference_vs_oracle_and_worst_is_recorded
+#                                  prints it: 3.039e-7 at (12, 12, 64), T = 3, eps 1e-5, with RoPE)
+QKNORM_SLACK = 2.0 ** -19        # 4 * 3.04e-7 = 1.22e-6 <= 2^-19 = 1.91e-6
+QKNORM_SHAPES = ((32, 8, 128), (4, 1, 128), (16, 8, 128), (40, 8, 128), (12, 12, 64), (1, 1, 64))    # hq, hkv, D
+QKNORM_T = (1, 3, 37)
+QKNORM_EPS = (1e-6, 1e-5)
+
+
+def qk_norm_rope(x: torch.Tensor, gq: torch.Tensor, gk: torch.Tensor, eps: float, cs: Optional[torch.Tensor],
+                 n_q: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp64 ``rope(rms_norm(x))`` of the q and k heads ``x`` [T, n_q + n_k, D] (q heads first; ``n_q``
+    None: every head is a q head): each head normalised over D with ``eps`` and scaled by ``gq`` [D]
+    (heads < n_q) or ``gk`` [D], then rotated by the fp32 table rows ``cs`` [T, D] (None: no rotation).
+    -> ``(e, mag)``, ``mag`` = :func:`rope`'s magnitude of the normalised values."""
+    n_q = x.shape[1] if n_q is None else n_q
+    yq, _ = rms_norm(x[:, :n_q], gq, eps)
+    yk, _ = rms_norm(x[:, n_q:], gk, eps)
+    return rope(torch.cat([yq, yk], dim=1), cs)
+
+
+def qk_norm_tol(e, mag):
+    return bf16_ulp(e) + QKNORM_SLACK * mag
+
+
+def qk_norm_gammas(D: int, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """bf16 ``(q_gamma, k_gamma)`` [D] around 1 with negative, zero and large entries in both (64 for q;
+    -16 for k, which keeps every normalised key of the test inputs below the fp8 cache's 448 x 0.37)."""
+    g = _gen(7100 + D + seed)
+    gq, gk = _randn((D,), g, 0.3, 1.0), _randn((D,), g, 0.3, 1.0)
+    gq[1], gq[D // 2 + 2], gq[5], gq[D - 1] = -0.75, 0.0, 64.0, -1.5
+    gk[0], gk[3], gk[D // 2], gk[D - 2] = 0.0, -16.0, 2.5, -0.5
+    return gq, gk
+
+
+def qk_norm_case(hq: int, hkv: int, D: int, T: int, seed: int = 0):
+    """:func:`rope_case` with the fixed rows of the QK-norm tests written into ``qkv`` (token 0, and
+    token T - 1 where T > 1): q head 0 holds one element 2^15 among values near 2^-8, the last k head is
+    all zero (its output is exactly zero under any eps > 0), and in the last token q head ``hq - 1``
+    sits at |x| = 2^60 (the sum of squares stays finite in fp32: 128 * 2^120 = 2^127; larger inputs are
+    outside the contract); in the one-head, one-token case that row replaces the first.
+    -> (qkv, positions, slots, k_cache, v_cache)."""
+    qkv, pos, slots, kc, vc = rope_case(hq, hkv, D, T, seed)
+    g = _gen(7200 + seed + 13 * hq + 7 * hkv + D + 1000 * T)
+    rows = qkv.view(T, hq + 2 * hkv, D)
+    small = _randn((D,), g, 2.0 ** -8)
+    small[D // 3] = 2.0 ** 15
+    rows[0, 0] = small
+    rows[0, hq + hkv - 1] = 0.0
+    sign = torch.where(torch.rand(D, generator=g) < 0.5, -1.0, 1.0)
+    rows[T - 1, hq - 1] = (sign * 2.0 ** 60).to(torch.bfloat16)
+    return qkv, pos, slots, kc, vc
+
+
 LOGIT_PROC_SLACK = 2.0 ** -22
 LOGIT_PROC_WINDOW = 2048
 LOGIT_PROC_MAX_BIAS = 300

@@ -130,6 +130,44 @@ def rope_and_cache(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: Optional
     return q.to(qkv.dtype)
 
 
+def qk_norm_rope_and_cache(qkv: torch.Tensor, q_gamma: torch.Tensor, k_gamma: torch.Tensor, eps: float,
+                           positions: torch.Tensor, cos_sin: Optional[torch.Tensor], k_cache: torch.Tensor,
+                           v_cache: torch.Tensor, slot_mapping: torch.Tensor, n_heads: int, n_kv_heads: int,
+                           head_dim: int, k_scale: float = 1.0, v_scale: float = 1.0) -> torch.Tensor:
+    """:func:`rope_and_cache` with a per-head RMSNorm of q and k first (Qwen3's q_norm / k_norm;
+    csrc/qk_norm_rope.hip). Per token and head, fp32 throughout: ``ss`` = the sum of the squares of the
+    head's ``head_dim`` inputs, ``r = rsqrt(ss / head_dim + eps)``, ``y = x * r * gamma`` (q heads:
+    ``q_gamma``, k heads: ``k_gamma``, both ``[head_dim]``; v is not normalised); ``y`` is rotated
+    (``cos_sin=None``: not) with NO rounding to bf16 between the norm and the rotation. q leaves as
+    ``qkv.dtype``, k and v go to the paged cache as :func:`rope_and_cache` writes them. ``qkv`` is
+    only read. Inputs whose sum of squares overflows fp32 (|x| above about 2^60 across a head) are
+    outside the contract."""
+    T = qkv.shape[0]
+    nq, nk = n_heads * head_dim, n_kv_heads * head_dim
+
+    def norm(x, gamma):
+        ss = x.pow(2).sum(-1, keepdim=True)
+        return x * torch.rsqrt(ss / head_dim + eps) * gamma.float()
+
+    q = norm(qkv[:, :nq].reshape(T, n_heads, head_dim).float(), q_gamma)
+    k = norm(qkv[:, nq:nq + nk].reshape(T, n_kv_heads, head_dim).float(), k_gamma)
+    v = qkv[:, nq + nk:].reshape(T, n_kv_heads, head_dim)
+    if cos_sin is not None:
+        cs = cos_sin[positions.long()]
+        q = _rotate(q, cs)
+        k = _rotate(k, cs)
+    bs = k_cache.shape[2]
+    slots = slot_mapping.long()
+    blk, off = slots // bs, slots % bs
+    if is_fp8_cache(k_cache, v_cache):
+        write_k_fp8(k_cache, blk, off, kv_fp8_code(k, kv_fp8_inv(k_scale)))
+        write_v_fp8(v_cache, blk, off, kv_fp8_code(v.float(), kv_fp8_inv(v_scale)))
+        return q.to(qkv.dtype)
+    write_k(k_cache, blk, off, k)
+    v_cache[blk, :, :, off] = v.to(v_cache.dtype)
+    return q.to(qkv.dtype)
+
+
 # ---- FP8 K/V cache (kv_dtype "fp8"; csrc/kv_fp8_core.h is the same rule on host and device) ----
 KV_FP8_MAX = 448.0        # largest finite OCP e4m3fn value
 KV_FP8_NAN = 0x7F

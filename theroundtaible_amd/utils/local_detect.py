@@ -11,7 +11,7 @@ knights, so discovery looks for *weights*: directories holding ``config.json`` p
 * the Hugging Face hub cache (``$HF_HOME``/``~/.cache/huggingface/hub/models--*/snapshots/*``).
 
 Each hit is read (JSON only — nothing from a checkpoint is executed) and matched to a preset
-(Llama-3-8B/70B, Mistral-7B, Qwen2.5-7B/0.5B, GPT-2) or described as a preset plus shape overrides; embedding /
+(Llama-3-8B/70B, Mistral-7B, Qwen2.5-7B/0.5B, Qwen3-0.6B..32B, GPT-2) or described as a preset plus shape overrides; embedding /
 reranker / speech models are skipped, as the reference's ``isNonChatModel`` does.
 Running servers are still supported from the other side: ``roundtable serve`` speaks the
 LM Studio / Ollama dialects.
@@ -97,9 +97,15 @@ def _rope_theta(hf: Dict[str, Any], default: float = 10000.0) -> float:
 
 def _shape_from_hf(hf: Dict[str, Any]) -> Optional[Dict[str, Any]]:
     mt = str(hf.get("model_type", "")).lower()
-    if mt in ("llama", "mistral", "qwen2"):
+    if mt in ("llama", "mistral", "qwen2", "qwen3"):
         if hf.get("attention_bias") or hf.get("mlp_bias"):
-            return None   # biased o / MLP projections (Llama variants): not in the engine's layer
+            return None   # biased o / MLP projections (Llama variants; Qwen3: biased q/k/v too): not in the engine's layer
+        if mt == "qwen3":
+            # dense Qwen3 with full attention in every layer only ("qwen3_moe" is another model_type)
+            layer_types = hf.get("layer_types")
+            if hf.get("use_sliding_window") or (isinstance(layer_types, (list, tuple))
+                                                and any(t != "full_attention" for t in layer_types)):
+                return None
         scaling = _rope_scaling(hf)
         if scaling is False:
             return None   # a RoPE scaling the engine does not implement
@@ -111,7 +117,7 @@ def _shape_from_hf(hf: Dict[str, Any]) -> Optional[Dict[str, Any]]:
                 "max_pos": int(hf.get("max_position_embeddings", 8192)),
                 "rope_theta": _rope_theta(hf), "norm_eps": float(hf.get("rms_norm_eps", 1e-5)),
                 "tie_embeddings": bool(hf.get("tie_word_embeddings", False)),
-                "qkv_bias": mt == "qwen2", "rope_scaling": scaling}
+                "qkv_bias": mt == "qwen2", "rope_scaling": scaling, "qk_norm": mt == "qwen3"}
     if mt == "gpt2":
         h = int(hf["n_embd"])
         nh = int(hf["n_head"])
@@ -123,10 +129,14 @@ def _shape_from_hf(hf: Dict[str, Any]) -> Optional[Dict[str, Any]]:
 
 
 def match_preset(shape: Dict[str, Any]) -> (Optional[str], Dict[str, Any]):
-    """Preset with the same architecture and fewest differing fields, plus those differences."""
+    """Preset with the same architecture and fewest differing fields, plus those differences.
+    ``qk_norm`` counts as architecture: a Qwen3 checkpoint lands on a ``qwen3-*`` preset whatever its
+    shape, and no other checkpoint does."""
     best, best_diff = None, None
     for name, cfg in PRESETS.items():
         if cfg.arch != shape["arch"] or name.startswith("tiny"):
+            continue
+        if cfg.qk_norm != bool(shape.get("qk_norm", False)):
             continue
         diff = {k: v for k, v in shape.items() if k != "arch" and getattr(cfg, k) != v}
         if best_diff is None or len(diff) < len(best_diff):
@@ -136,7 +146,7 @@ def match_preset(shape: Dict[str, Any]) -> (Optional[str], Dict[str, Any]):
 
 def checkpoint_model(path: str) -> Optional[tuple]:
     """(engine preset, ModelConfig overrides) for an HF checkpoint directory, from its
-    ``config.json`` alone; None if it is not a recognised Llama / Mistral / Qwen2 / GPT-2 checkpoint."""
+    ``config.json`` alone; None if it is not a recognised Llama / Mistral / Qwen2 / Qwen3 / GPT-2 checkpoint."""
     try:
         with open(os.path.join(path, "config.json"), encoding="utf-8") as f:
             shape = _shape_from_hf(json.load(f))
